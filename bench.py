@@ -12,9 +12,16 @@ paths = 2M path-labels per step in total (strong scaling), rank r owning MC indi
 RCCL + dpi_moments_reduce (`--workload burgers_cfg3` runs the same at N = 1; `--workload burgers`
 at N > 1 is the weak-scaling variant, 4096 paths per GPU).
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps and prints the result line.  `--full` adds what
+takes runs of its own after the timed region: the parity of the first timed batch against the fp64
+oracle (N > 1: also against one call over all paths), the exact-fp32 pass, the u = 0 noise-floor
+launches and the CPU baseline.  `--dump-outputs DIR` writes the last timed step's points and labels
+(what the caller of that step receives) as DIR/tx.npy and DIR/y.npy; the timed steps draw their
+points from fixed Philox counters, so two runs with the same arguments see the same inputs.
 
 Rehearsal of the N > 1 path on ONE GPU (RCCL refuses two ranks on one device):
 DPI_BENCH_BACKEND=gloo DPI_BENCH_SHARE_GPU=1 with torch.distributed.run --nproc-per-node 2 runs both
@@ -44,6 +51,7 @@ PEAK_SPLIT_TFLOPS = PEAK_F16_TFLOPS / 3.0
 PEAK_HBM_GBS = 8000.0
 N_SIMD = 1024          # 256 CUs x 4 SIMDs
 PEAK_CLOCK_GHZ = 2.4   # MI355X peak engine clock (MI355X_MICROARCH.md)
+TIMED_POINT_BASE = 1 << 24  # Philox point counter at which the warmup and the timed steps start
 # workloads = BASELINE.json configs; FLOP per path-label from SURVEY.md §8(d), except GBM, whose
 # kernel runs a cheaper algorithm than §8(d) assumes (adjoint + first-order tangents instead of
 # second-order forward mode): there the FLOPs it executes are counted.
@@ -89,7 +97,12 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need, after the timed region: oracle parity "
+                         "of the first timed batch, the exact-fp32 pass, the u = 0 noise floor, the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's points and labels as DIR/tx.npy and DIR/y.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--prewarm-s", type=float, default=0.3, help="untimed steps for this long before the warmup")
     ap.add_argument("--cpu-sample-paths", type=int, default=512, help="MC paths per point in the CPU sample")
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default=None,
@@ -106,7 +119,8 @@ def parse():
                          "LabelBuffer.fill checks one Picard iteration's labels; 'step' = one group per step, "
                          "verified one step behind, as the dataset surface checks each label buffer; 'off' = "
                          "unguarded (finiteness asserted afterwards)")
-    ap.add_argument("--no-fp32-pass", action="store_true", help="skip the untimed exact-fp32 comparison pass")
+    ap.add_argument("--no-fp32-pass", action="store_true",
+                    help="with --full: skip the untimed exact-fp32 comparison pass")
     return ap.parse_args()
 
 
@@ -319,13 +333,15 @@ def main():
 
     # (tx, point_base) of every begun batch, in order; the labels come out in the same order.  The
     # first timed batch's points and labels are kept for the parity check after the timed region.
-    begun, capture = [], {}
+    # The last finished batch's points and labels are what --dump-outputs writes.
+    begun, capture, last = [], {}, {}
 
     def finish(handle):
         y = handle[1] if isinstance(handle[0], str) else labeler.end(handle)
         tx_, pb_ = begun.pop(0)
         if capture.get("armed") and "y" not in capture:
             capture.update(tx=tx_, pb=pb_, y=y)
+        last["tx"], last["y"] = tx_, y
         return y
 
     # The path launch of every EV_EVERY-th step is timed: events on the dispatch packet at that rate
@@ -416,6 +432,14 @@ def main():
             dist.broadcast(go, src=0)
         if go.item() == 0.0:
             break
+    # The prewarm runs for a wall time, so it ends at another Philox point counter in every run.  The
+    # warmup and the timed steps start from a fixed one (past any prewarm's), which makes their
+    # points, and so the labels --dump-outputs writes, the same from run to run.
+    drain()
+    torch.cuda.synchronize()
+    gen.point_base = TIMED_POINT_BASE
+    labeler._ahead = None  # points sampled ahead at the prewarm's counter
+    open_region()
     for _ in range(args.warmup):
         step()
     drain()
@@ -442,8 +466,17 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt, k_ms = float(t[0]), float(t[1])
     assert torch.isfinite(y).all()
-    parity = live_parity(wl, eq, net, capture["tx"], capture["pb"], capture["y"], M) if rank == 0 else None
-    if rank == 0 and world > 1:
+    if args.dump_outputs and rank == 0:
+        # the last timed step's (points, labels), as its caller receives them (every rank holds the same)
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, t in (("tx", last["tx"]), ("y", last["y"])):
+            t = t.detach().cpu()
+            np.save(os.path.join(args.dump_outputs, f"{name}.npy"),
+                    t.to(torch.float64 if t.dtype == torch.float64 else torch.float32).numpy())
+    parity = (live_parity(wl, eq, net, capture["tx"], capture["pb"], capture["y"], M)
+              if rank == 0 and args.full else None)
+    if rank == 0 and world > 1 and args.full:
         # the sharded labels against ONE call over all M paths of the same batch on this GPU (after
         # the timed region): bit-identical when M / (64 N) is a power of two
         one = ShardedLabeler(gen, rank=0, world=1)
@@ -456,7 +489,7 @@ def main():
     # What the fp16-split MFMA buys: the same schedule with this net on exact-fp32 MFMA
     # (dpi_net_set_precision, = DPI_GEMM=f32), untimed by the contract's clock, after the timed region
     exact_fp32_ms = None
-    if not args.no_fp32_pass and os.environ.get("DPI_GEMM", "") != "f32":
+    if args.full and not args.no_fp32_pass and os.environ.get("DPI_GEMM", "") != "f32":
         gen.net.set_precision(L.DPI_GEMM_F32)
         for _ in range(2):
             step()
@@ -478,7 +511,7 @@ def main():
             exact_fp32_ms = float(t[0])
         gen.net.set_precision(-1)
     floor_ms = None
-    if rank == 0 and not wl.get("pis") and not wl.get("hess") and "m_total" not in wl:
+    if args.full and rank == 0 and not wl.get("pis") and not wl.get("hess") and "m_total" not in wl:
         gen0 = dpi.OnlineDataGenerator(eq, dpi.ZeroSolution(1), 80, 1, device=dev, t_always_uniform=True,
                                        n_estimate_terminal=M_PER_GPU, n_estimate_integral=M_PER_GPU,
                                        n_euler_steps=K_STEPS, seed=1, hessian_approximation=hess)
@@ -564,6 +597,7 @@ def main():
             "steps": args.steps,
             "warmup": args.warmup,
             "ms_per_step": ms_step,
+            "full": args.full,
             "higher_is_better": True,
             "scaling": wl.get("scaling", "weak"),
             "vs_baseline": None,
@@ -616,7 +650,7 @@ def main():
                 "what": "same launch with u = 0 (ZeroSolution): Philox4x32-10 + Box-Muller + K-step EM only, the "
                         "VALU-issue floor of the noise contract (2 x K x nx normals per path-label)",
                 "kernel_ms": floor_ms, "frac": floor_ms / k_ms}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(wl, args.cpu_sample_paths if wl["eq"] == "Cha" else 64)
         print(json.dumps(out), flush=True)
     if dist:

@@ -8,6 +8,12 @@ from deeppicarditeration_amd.config import get_default_cfg, load_cfg
 from deeppicarditeration_amd.main import main
 
 REF_SCRIPTS = "/root/reference/scripts"
+# The experiment YAMLs the reference ships (settings only) are stored as fixtures and read from
+# there alone.  REF_SCRIPTS is where they came from: it only names the cases, so that each keeps
+# the id it had when the files were read in place.
+FIXTURES = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_scripts")
+REF_YAMLS = sorted(os.path.relpath(p, FIXTURES).replace(os.sep, "/")
+                   for p in glob.glob(f"{FIXTURES}/**/*.yaml", recursive=True))
 
 
 def _write(p, text):
@@ -61,10 +67,14 @@ def test_reserved_memory_compat(tmp_path):
         load_cfg(g)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_SCRIPTS), reason="reference experiment YAMLs not present")
-@pytest.mark.parametrize("path", sorted(glob.glob(f"{REF_SCRIPTS}/**/*.yaml", recursive=True)))
+def test_reference_yaml_fixtures_present():
+    assert len(REF_YAMLS) == 13
+
+
+@pytest.mark.parametrize("path", REF_YAMLS, ids=[f"{REF_SCRIPTS}/{p}" for p in REF_YAMLS])
 def test_reference_yamls_load(path):
     """Every experiment YAML the reference ships loads into this schema unchanged (read as data)."""
+    path = os.path.join(FIXTURES, path)
     cwd = os.getcwd()
     try:
         os.chdir(os.path.dirname(path))

@@ -15,7 +15,7 @@ for wl in ("burgers", "burgers_cfg3", "hjb", "gbm", "gbm_hess", "hjb_onestream")
     f = src / f"trace_{wl}" / "trace_kernel_stats.csv"
     if f.exists():
         rows = list(csv.DictReader(open(f)))
-        out = {"command": f"rocprofv3 --kernel-trace --stats -- python bench.py --workload {wl.split('_one')[0]} "
+        out = {"command": f"rocprofv3 --kernel-trace --stats -- python bench.py --full --workload {wl.split('_one')[0]} "
                           f"--steps 10 --warmup 2 --no-cpu-baseline{' --no-prepare' if 'onestream' in wl else ''}",
                "kernels": [{"name": r["Name"][:160], "calls": int(r["Calls"]), "avg_us": float(r["AverageNs"]) / 1e3,
                             "min_us": float(r["MinNs"]) / 1e3, "max_us": float(r["MaxNs"]) / 1e3,
@@ -42,7 +42,7 @@ for wl, anchor in ANCHOR.items():
         pmc[c] = {k: {"dispatches": len(v), "total_kb": sum(v)} for k, v in agg.items()}
         (dst / f"{tag}_pmc_{wl}_{c}.json").write_text(json.dumps(
             {"command": f"rocprofv3 --pmc {c} --kernel-include-regex 'k_paths|k_pis|k_gemm|k_reduce|k_noise' -- python "
-                        f"bench.py --workload {wl} --steps 10 --warmup 2 --no-cpu-baseline", "kernels": pmc[c]},
+                        f"bench.py --full --workload {wl} --steps 10 --warmup 2 --no-cpu-baseline", "kernels": pmc[c]},
             indent=1))
     if len(pmc) < 2:
         continue
@@ -79,7 +79,7 @@ for wl in ("burgers", "burgers_cfg3", "gbm", "gbm_hess"):
     for (name, _), c in per.items():
         kinds[name].append(c)
     out = {"command": f"rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_MFMA SQ_ACTIVE_INST_VALU SQ_BUSY_CYCLES "
-                      f"SQ_WAVE_CYCLES GRBM_GUI_ACTIVE --kernel-include-regex 'k_paths|k_noise' -- python bench.py --workload {wl} "
+                      f"SQ_WAVE_CYCLES GRBM_GUI_ACTIVE --kernel-include-regex 'k_paths|k_noise' -- python bench.py --full --workload {wl} "
                       "--steps 10 --warmup 2 --no-cpu-baseline",
            "units": "per launch; valu_busy_cycles_per_simd = SQ_ACTIVE_INST_VALU x 4 / 1024 SIMDs; kernel_cycles = "
                     "GRBM_GUI_ACTIVE / 8 XCDs; valu_busy = their ratio (the rocprofv3 VALUBusy expression)",

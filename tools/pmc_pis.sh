@@ -7,6 +7,6 @@ for set in "SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_ACTIVE_INST_VALU SQ_INSTS_
            "FETCH_SIZE" "WRITE_SIZE"; do
   p=$((p+1))
   timeout -s KILL 120 rocprofv3 --pmc $set --kernel-include-regex "k_pis_final|k_pis_time|k_pis_base" -d $out/p$p -o pmc --output-format csv -- \
-    python bench.py --workload hjb --steps 4 --warmup 1 --no-cpu-baseline --no-prepare > $out/p$p.log 2>&1 || echo "pass $p rc=$?"
+    python bench.py --full --workload hjb --steps 4 --warmup 1 --no-cpu-baseline --no-prepare > $out/p$p.log 2>&1 || echo "pass $p rc=$?"
 done
 echo done

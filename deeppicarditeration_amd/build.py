@@ -1,7 +1,7 @@
 """Build libdpi_hip.so in-tree for gfx950 (hipcc cross-compiles without a GPU).
 
-Thirteen translation units (the C-ABI / PIS / reduce TU, and per equation the k_paths family, its
-TD-estimator family and the Tanh-activation twins of both) compile in parallel to objects, then link into one
+The translation units of `UNITS` (the C-ABI / PIS / reduce TU, and one `dpi_paths_*.hip` per row of the
+unit table in `csrc/dpi_dispatch.h`) compile in parallel to objects, then link into one
 shared library together with a generated one-function unit, `dpi_build_id()`, that returns the
 SHA-256 of the sources and flags (`source_hash`).  A build is current when the library itself
 embeds the tree's hash (not by mtime, and not by a side file that a checkout could leave behind

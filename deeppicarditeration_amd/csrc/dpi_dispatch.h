@@ -1,6 +1,6 @@
 // Host-side handles and the (equation, network shape) -> k_paths / k_baseline instantiation
-// dispatch; dispatch<KIND> is instantiated once per equation kind in dpi_paths_{cha,ou,gbm}.hip
-// so the three families compile in parallel.
+// dispatch; dpi_dispatch is instantiated once per row of the unit table (DPI_UNITS, below), each in
+// a dpi_paths_*.hip unit of its own, so the families compile in parallel.
 #pragma once
 #include <hip/hip_ext.h>
 
@@ -33,13 +33,13 @@ constexpr int STATUS_STRIDE = 16;  // ints per ring slot (64 B)
 
 // ---- dispatch over (equation, network shape)
 struct Launch {
-  bool baseline;
-  const float* tx;
-  int n;
-  float *gx, *fb, *bx, *hb;
-  const PathArgs* a;
-  int nblocks;
-  hipStream_t st;
+  bool baseline = false;
+  const float* tx = nullptr;
+  int n = 0;
+  float *gx = nullptr, *fb = nullptr, *bx = nullptr, *hb = nullptr;
+  const PathArgs* a = nullptr;
+  int nblocks = 0;
+  hipStream_t st = nullptr;
   bool hess = false;  // k_paths in Hessian-label mode (GBM only)
   bool td = false;    // k_paths with the TD estimators (problem td_dt > 0)
   SampleSpec smp{};   // baseline: sample the points in the same launch (smp.tx != null)
@@ -61,12 +61,23 @@ struct Launch {
 // FBV: k_paths_fb, the one-launch sample_with_gradients (q.fbase), in translation units of its own
 // (dpi_paths_fb_*.hip: beside the plain kernels it perturbed their register allocation — the
 // OU 4 x 128 split instance went from 255 VGPRs to 256 and 3 spilled).  Instantiated where
-// fused_base_shape holds, which is where dpi_kernels.hip fused_base_ok selects it: Cha / OU with
-// ELU, zero nets and the fp16-split MLP instances (H % 32 == 0) — except OU 4 x 128, whose GMM
-// statistics beside the hand-off spill 3 VGPRs at two workgroups per CU (it keeps two launches).
-template <int KIND, int H, int L, bool Z, int ACT>
-constexpr bool fused_base_shape() {
-  return KIND != DPI_EQ_GBM && ACT == DPI_ACT_ELU && (Z || (H % 32 == 0 && !(KIND == DPI_EQ_OU && H == 128 && L == 4)));
+// fused_base_shape holds, and dpi_kernels.hip fused_base_ok selects it by the same function: Cha /
+// OU with ELU, zero nets and the fp16-split MLP instances (H % 32 == 0) — except OU 4 x 128, whose
+// GMM statistics beside the hand-off spill 3 VGPRs at two workgroups per CU (it keeps two launches).
+constexpr bool fused_base_shape(int kind, int H, int L, bool zero, int act) {
+  return kind != DPI_EQ_GBM && act == DPI_ACT_ELU && (zero || (H % 32 == 0 && !(kind == DPI_EQ_OU && H == 128 && L == 4)));
+}
+// The k_paths instance of a unit's <HESS, TD, NXW> for one net shape.  The one run-time bit is the
+// fp16-split mode (q.a->split), which has an instance of its own where !Z && H % 32 == 0.
+template <int KIND, int H, int L, bool Z, int ACT, bool HESS, bool TD, int NXW>
+void launch_paths(const EqDev& e, const dpi_net_s* net, const Launch& q) {
+  if constexpr (!Z && H % 32 == 0) {
+    if (q.a->split) {
+      DPI_PATH_LAUNCH((k_paths<KIND, H, L, Z, true, HESS, TD, ACT, NXW>), q, e, net->d, *q.a);
+      return;
+    }
+  }
+  DPI_PATH_LAUNCH((k_paths<KIND, H, L, Z, false, HESS, TD, ACT, NXW>), q, e, net->d, *q.a);
 }
 // NXW > NXP_MAX: the wide first-order instances (Cha / OU, nx up to NXW_MAX; dpi_paths_wide_*.hip):
 // plain k_paths only — the baseline is shape-generic, the TD / Hessian / fused-baseline forms have none.
@@ -74,30 +85,17 @@ template <int KIND, int H, int L, bool Z, bool TDV, int ACT = DPI_ACT_ELU, bool 
 void do_launch(const dpi_problem_s* p, const dpi_net_s* net, const Launch& q) {
   if constexpr (NXW > NXP_MAX) {
     static_assert(!TDV && !FBV, "wide instances: first-order labels");
-    if constexpr (!Z && H % 32 == 0) {
-      if (q.a->split) {
-        DPI_PATH_LAUNCH((k_paths<KIND, H, L, Z, true, false, false, ACT, NXW>), q, p->e, net->d, *q.a);
-        return;
-      }
-    }
-    DPI_PATH_LAUNCH((k_paths<KIND, H, L, Z, false, false, false, ACT, NXW>), q, p->e, net->d, *q.a);
+    launch_paths<KIND, H, L, Z, ACT, false, false, NXW>(p->e, net, q);
   } else if constexpr (FBV) {
-    if constexpr (fused_base_shape<KIND, H, L, Z, ACT>())
+    if constexpr (fused_base_shape(KIND, H, L, Z, ACT))
       DPI_PATH_LAUNCH((k_paths_fb<KIND, H, L, Z, !Z, ACT>), q, p->e, net->d, *q.a,
                          *q.fbase);
   } else if constexpr (TDV) {
-    if constexpr (!Z && H % 32 == 0) {
-      if (q.a->split)
-        DPI_PATH_LAUNCH((k_paths<KIND, H, L, Z, true, false, true, ACT>), q, p->e,
-                           net->d, *q.a);
-      else
-        DPI_PATH_LAUNCH((k_paths<KIND, H, L, Z, false, false, true, ACT>), q, p->e, net->d, *q.a);
-    } else {
-      DPI_PATH_LAUNCH((k_paths<KIND, H, L, Z, false, false, true, ACT>), q, p->e,
-                         net->d, *q.a);
-    }
+    launch_paths<KIND, H, L, Z, ACT, false, true, NXW>(p->e, net, q);
   } else if (q.baseline) {
-    if constexpr (KIND == DPI_EQ_GBM) {
+    if constexpr (ACT != DPI_ACT_ELU)
+      return;  // activation-generic: the ELU units hold it (dpi_dispatch refuses it in the Tanh units first)
+    else if constexpr (KIND == DPI_EQ_GBM) {
       if (p->e.nx > NXP_MAX)  // the wide baseline (nx <= 256)
         hipLaunchKernelGGL((k_baseline_gbm<Z, NXW_MAX>), dim3(q.n), dim3(NTHB), 0, q.st, p->e, net->d, q.tx, q.n, q.gx,
                            q.fb, q.bx, q.hb, q.smp, q.tickets);
@@ -112,24 +110,10 @@ void do_launch(const dpi_problem_s* p, const dpi_net_s* net, const Launch& q) {
     if constexpr (KIND == DPI_EQ_GBM) {
       EqDev e2 = p->e;
       e2.sdgd_v = 0;  // the Hessian estimators evaluate f with the full Hessian (data.py:856, :1262-1272)
-      if constexpr (!Z && H % 32 == 0) {
-        if (q.a->split) {
-          DPI_PATH_LAUNCH((k_paths<KIND, H, L, Z, true, true, false, ACT>), q, e2, net->d, *q.a);
-          return;
-        }
-      }
-      DPI_PATH_LAUNCH((k_paths<KIND, H, L, Z, false, true, false, ACT>), q, e2,
-                         net->d, *q.a);
+      launch_paths<KIND, H, L, Z, ACT, true, false, NXW>(e2, net, q);
     }
-  } else if constexpr (!Z && H % 32 == 0) {
-    if (q.a->split)
-      DPI_PATH_LAUNCH((k_paths<KIND, H, L, Z, true, false, false, ACT>), q, p->e,
-                         net->d, *q.a);
-    else
-      DPI_PATH_LAUNCH((k_paths<KIND, H, L, Z, false, false, false, ACT>), q, p->e, net->d, *q.a);
   } else
-    DPI_PATH_LAUNCH((k_paths<KIND, H, L, Z, false, false, false, ACT>), q, p->e,
-                       net->d, *q.a);
+    launch_paths<KIND, H, L, Z, ACT, false, false, NXW>(p->e, net, q);
 }
 
 template <int KIND, bool TDV = false, int ACT = DPI_ACT_ELU, bool FBV = false, int NXW = NXP_MAX>
@@ -182,23 +166,65 @@ bool dpi_dispatch(const dpi_problem_s* p, const dpi_net_s* net, const Launch& q)
   }
 }
 
-bool dispatch_cha(const dpi_problem_s* p, const dpi_net_s* net, const Launch& q);
-bool dispatch_ou(const dpi_problem_s* p, const dpi_net_s* net, const Launch& q);
-bool dispatch_gbm(const dpi_problem_s* p, const dpi_net_s* net, const Launch& q);
-bool dispatch_td_cha(const dpi_problem_s* p, const dpi_net_s* net, const Launch& q);
-bool dispatch_td_ou(const dpi_problem_s* p, const dpi_net_s* net, const Launch& q);
-bool dispatch_td_gbm(const dpi_problem_s* p, const dpi_net_s* net, const Launch& q);
-bool dispatch_cha_tanh(const dpi_problem_s* p, const dpi_net_s* net, const Launch& q);
-bool dispatch_ou_tanh(const dpi_problem_s* p, const dpi_net_s* net, const Launch& q);
-bool dispatch_gbm_tanh(const dpi_problem_s* p, const dpi_net_s* net, const Launch& q);
-bool dispatch_td_cha_tanh(const dpi_problem_s* p, const dpi_net_s* net, const Launch& q);
-bool dispatch_td_ou_tanh(const dpi_problem_s* p, const dpi_net_s* net, const Launch& q);
-bool dispatch_td_gbm_tanh(const dpi_problem_s* p, const dpi_net_s* net, const Launch& q);
-bool dispatch_fb_cha(const dpi_problem_s* p, const dpi_net_s* net, const Launch& q);
-bool dispatch_fb_ou(const dpi_problem_s* p, const dpi_net_s* net, const Launch& q);
-bool dispatch_wide_cha(const dpi_problem_s* p, const dpi_net_s* net, const Launch& q);
-bool dispatch_wide_ou(const dpi_problem_s* p, const dpi_net_s* net, const Launch& q);
-bool dispatch_wide_cha_tanh(const dpi_problem_s* p, const dpi_net_s* net, const Launch& q);
-bool dispatch_wide_ou_tanh(const dpi_problem_s* p, const dpi_net_s* net, const Launch& q);
-bool dispatch_wide_gbm(const dpi_problem_s* p, const dpi_net_s* net, const Launch& q);
-bool dispatch_wide_gbm_tanh(const dpi_problem_s* p, const dpi_net_s* net, const Launch& q);
+// ---- the unit table: one row per dpi_paths_*.hip translation unit, keyed by dpi_dispatch's template
+// arguments (KIND, TDV, ACT, FBV, NXW).  Each unit file holds the explicit instantiation of its row
+// (DPI_UNIT_DEFINE) and nothing else; every other unit sees the row as an extern template, so a row
+// without a unit fails at link time.  dpi_kernels.hip dispatch_any derives the key of a launch and
+// looks it up here.
+#define DPI_UNITS(X)                                                \
+  X(cha, DPI_EQ_CHA, false, DPI_ACT_ELU, false, NXP_MAX)            \
+  X(ou, DPI_EQ_OU, false, DPI_ACT_ELU, false, NXP_MAX)              \
+  X(gbm, DPI_EQ_GBM, false, DPI_ACT_ELU, false, NXP_MAX)            \
+  X(td_cha, DPI_EQ_CHA, true, DPI_ACT_ELU, false, NXP_MAX)          \
+  X(td_ou, DPI_EQ_OU, true, DPI_ACT_ELU, false, NXP_MAX)            \
+  X(td_gbm, DPI_EQ_GBM, true, DPI_ACT_ELU, false, NXP_MAX)          \
+  X(cha_tanh, DPI_EQ_CHA, false, DPI_ACT_TANH, false, NXP_MAX)      \
+  X(ou_tanh, DPI_EQ_OU, false, DPI_ACT_TANH, false, NXP_MAX)        \
+  X(gbm_tanh, DPI_EQ_GBM, false, DPI_ACT_TANH, false, NXP_MAX)      \
+  X(td_cha_tanh, DPI_EQ_CHA, true, DPI_ACT_TANH, false, NXP_MAX)    \
+  X(td_ou_tanh, DPI_EQ_OU, true, DPI_ACT_TANH, false, NXP_MAX)      \
+  X(td_gbm_tanh, DPI_EQ_GBM, true, DPI_ACT_TANH, false, NXP_MAX)    \
+  X(fb_cha, DPI_EQ_CHA, false, DPI_ACT_ELU, true, NXP_MAX)          \
+  X(fb_ou, DPI_EQ_OU, false, DPI_ACT_ELU, true, NXP_MAX)            \
+  X(wide_cha, DPI_EQ_CHA, false, DPI_ACT_ELU, false, NXW_MAX)       \
+  X(wide_ou, DPI_EQ_OU, false, DPI_ACT_ELU, false, NXW_MAX)         \
+  X(wide_gbm, DPI_EQ_GBM, false, DPI_ACT_ELU, false, NXW_MAX)       \
+  X(wide_cha_tanh, DPI_EQ_CHA, false, DPI_ACT_TANH, false, NXW_MAX) \
+  X(wide_ou_tanh, DPI_EQ_OU, false, DPI_ACT_TANH, false, NXW_MAX)   \
+  X(wide_gbm_tanh, DPI_EQ_GBM, false, DPI_ACT_TANH, false, NXW_MAX)
+
+struct Unit {
+  int kind;
+  bool td;
+  int act;
+  bool fb;
+  int nxw;
+  bool (*dispatch)(const dpi_problem_s*, const dpi_net_s*, const Launch&);
+  constexpr bool is(int k, bool t, int a, bool f, int w) const {
+    return kind == k && td == t && act == a && fb == f && nxw == w;
+  }
+};
+#define DPI_UNIT_EXTERN(NAME, ...) \
+  extern template bool dpi_dispatch<__VA_ARGS__>(const dpi_problem_s*, const dpi_net_s*, const Launch&);
+#define DPI_UNIT_ID(NAME, ...) UNIT_##NAME,
+#define DPI_UNIT_ROW(NAME, ...) {__VA_ARGS__, &dpi_dispatch<__VA_ARGS__>},
+DPI_UNITS(DPI_UNIT_EXTERN)
+enum UnitId { DPI_UNITS(DPI_UNIT_ID) N_UNITS };
+constexpr Unit UNITS[N_UNITS] = {DPI_UNITS(DPI_UNIT_ROW)};
+#undef DPI_UNIT_EXTERN
+#undef DPI_UNIT_ID
+#undef DPI_UNIT_ROW
+
+constexpr bool units_distinct() {
+  for (int i = 0; i < N_UNITS; ++i)
+    for (int j = 0; j < i; ++j)
+      if (UNITS[i].is(UNITS[j].kind, UNITS[j].td, UNITS[j].act, UNITS[j].fb, UNITS[j].nxw)) return false;
+  return true;
+}
+static_assert(units_distinct(), "two rows of DPI_UNITS share a (KIND, TDV, ACT, FBV, NXW) key");
+
+// The whole of dpi_paths_<NAME>.hip: the row's template arguments are written in DPI_UNITS only.
+#define DPI_UNIT_DEFINE(NAME)                                                                                   \
+  template bool dpi_dispatch<UNITS[UNIT_##NAME].kind, UNITS[UNIT_##NAME].td, UNITS[UNIT_##NAME].act,            \
+                             UNITS[UNIT_##NAME].fb, UNITS[UNIT_##NAME].nxw>(const dpi_problem_s*, const dpi_net_s*, \
+                                                                            const Launch&);

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <climits>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -229,6 +230,18 @@ static int fail(int code, const std::string& msg) {
     hipError_t _e = (x);                                                                             \
     if (_e != hipSuccess) return fail(DPI_ERR_HIP, std::string(#x) + ": " + hipGetErrorString(_e)); \
   } while (0)
+
+// The integer / real environment knobs: unset gives dflt, a set value is clamped
+// to [lo, hi].  A knob read once per process keeps the result in a function-local static; the ones
+// a test flips inside one process call these afresh.
+static int env_int(const char* name, int dflt, int lo = INT_MIN, int hi = INT_MAX) {
+  const char* e = std::getenv(name);
+  return e ? std::max(lo, std::min(hi, std::atoi(e))) : dflt;
+}
+static double env_real(const char* name, double dflt, double lo, double hi) {
+  const char* e = std::getenv(name);
+  return e ? std::max(lo, std::min(hi, std::atof(e))) : dflt;
+}
 
 template <typename T>
 static int upload(dpi_problem_s* p, const std::vector<T>& v, const T** out) {
@@ -1211,12 +1224,8 @@ static PisRows pis_rows_layout(const NetPisDev& pd, bool x3) {
 // workgroups, so launch gaps and the last-round tail are amortised.  Measured on HJB configs[2]
 // (ms/step): 256 -> 8.57, 512 -> 6.93, 1024 -> 6.41, 4096 -> 6.36.  DPI_PIS_CHUNK overrides.
 static int pis_chunk_wg() {
-  static const int v = [] {
-    const char* e = std::getenv("DPI_PIS_CHUNK");
-    const int x = e ? std::atoi(e) : 4096;
-    return x >= 1 ? x : 4096;
-  }();
-  return v;
+  static const int x = env_int("DPI_PIS_CHUNK", 4096);
+  return x >= 1 ? x : 4096;
 }
 
 // Workspace: gx[n] | fb[n] | bx[n][H] | hb[n][HBS = 256] | tickets[n] | rec[n][BREC] | ready[n] |
@@ -1229,12 +1238,8 @@ static size_t al256(size_t x) { return (x + 255) & ~size_t(255); }
 // GBM MLP nets stage their noise sums on the prepare stream (dpi_label_prepare -> k_noise_shared;
 // DPI_GBM_PREP=0 disables it): the workspace then holds them, [n][nbp][2][4 nb][P] floats.
 static bool gbm_noise_prep(dpi_problem p, dpi_net net) {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = std::getenv("DPI_GBM_PREP");
-    v = (!e || std::atoi(e) != 0) ? 1 : 0;
-  }
-  return v && p && net && net->d.kind == 1 && p->e.kind == DPI_EQ_GBM;
+  static const bool on = env_int("DPI_GBM_PREP", 1) != 0;
+  return on && p && net && net->d.kind == 1 && p->e.kind == DPI_EQ_GBM;
 }
 static WsLayout ws_layout(dpi_net net, int n, int M, int F, bool noise = false) {
   WsLayout w;
@@ -1296,15 +1301,24 @@ extern "C" int dpi_set_gemm_precision(int mode) {
   return 0;
 }
 
+// The GEMM launches' run-time epilogue as the kernels' EPI_* template constant: f(integral_constant).
+template <class F>
+static void with_epi(int epi, F f) {
+  if (epi == EPI_BIAS)
+    f(std::integral_constant<int, EPI_BIAS>{});
+  else if (epi == EPI_BIAS_ELU)
+    f(std::integral_constant<int, EPI_BIAS_ELU>{});
+  else
+    f(std::integral_constant<int, EPI_DELU>{});
+}
+
 static void gemm(int epi, int M, int N, int K, const float* A, int lda, const float* B, int ldb, float* C, int ldc,
                  const float* bias, const float* aux, int ldaux, hipStream_t st) {
   dim3 grid((M + GBM_ - 1) / GBM_, (N + GBN_ - 1) / GBN_), block(256);
-  if (epi == EPI_BIAS)
-    hipLaunchKernelGGL(k_gemm_nt<EPI_BIAS>, grid, block, 0, st, M, N, K, A, lda, B, ldb, C, ldc, bias, aux, ldaux);
-  else if (epi == EPI_BIAS_ELU)
-    hipLaunchKernelGGL(k_gemm_nt<EPI_BIAS_ELU>, grid, block, 0, st, M, N, K, A, lda, B, ldb, C, ldc, bias, aux, ldaux);
-  else
-    hipLaunchKernelGGL(k_gemm_nt<EPI_DELU>, grid, block, 0, st, M, N, K, A, lda, B, ldb, C, ldc, bias, aux, ldaux);
+  with_epi(epi, [&](auto e) {
+    hipLaunchKernelGGL(k_gemm_nt<decltype(e)::value>, grid, block, 0, st, M, N, K, A, lda, B, ldb, C, ldc, bias, aux,
+                       ldaux);
+  });
 }
 
 static int cu_count() {
@@ -1321,22 +1335,14 @@ static int cu_count() {
 // DELU epilogue operands staged through the ring's last two DMA slots (k_gemm_x3); DPI_X3_STAGE=0
 // loads them in the epilogue instead (ablation).
 static int x3_stage_aux() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = std::getenv("DPI_X3_STAGE");
-    v = e ? (std::atoi(e) != 0) : 1;
-  }
+  static const int v = env_int("DPI_X3_STAGE", 1) != 0;
   return v;
 }
 
 // Block tile of the NT = 4 split GEMMs: 128 (default, k_gemm_x3h: two blocks per CU) or 256
 // (DPI_X3_TILE=256: k_gemm_x3, one 8-wave block per CU with the staged DELU epilogue).
 static int x3_tile_rows() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = std::getenv("DPI_X3_TILE");
-    v = (e && std::atoi(e) == 256) ? 256 : 128;
-  }
+  static const int v = env_int("DPI_X3_TILE", 128) == 256 ? 256 : 128;
   return v;
 }
 
@@ -1350,28 +1356,19 @@ static void gemm_x3_nt(int epi, int M, int Kp, int Np, const uint32_t* W, float 
     if (x3_tile_rows() == 128) {
       const int nmh = (M + X3H_BM - 1) / X3H_BM;
       dim3 gh(nnt * nmh), bh(X3H_THREADS);
-      if (epi == EPI_BIAS)
-        hipLaunchKernelGGL(k_gemm_x3h<EPI_BIAS>, gh, bh, 0, st, M, Kp, nnt, W, ws, X, ldx, X2, ldx2, nk1, OUT, ldc, bias,
-                           aux, ldaux, os, as);
-      else if (epi == EPI_BIAS_ELU)
-        hipLaunchKernelGGL(k_gemm_x3h<EPI_BIAS_ELU>, gh, bh, 0, st, M, Kp, nnt, W, ws, X, ldx, X2, ldx2, nk1, OUT, ldc,
-                           bias, aux, ldaux, os, as);
-      else
-        hipLaunchKernelGGL(k_gemm_x3h<EPI_DELU>, gh, bh, 0, st, M, Kp, nnt, W, ws, X, ldx, X2, ldx2, nk1, OUT, ldc, bias,
-                           aux, ldaux, os, as);
+      with_epi(epi, [&](auto e) {
+        hipLaunchKernelGGL(k_gemm_x3h<decltype(e)::value>, gh, bh, 0, st, M, Kp, nnt, W, ws, X, ldx, X2, ldx2, nk1, OUT,
+                           ldc, bias, aux, ldaux, os, as);
+      });
       return;
     }
   }
   dim3 grid(nnt * nmt), block(X3_THREADS);
-  if (epi == EPI_BIAS)
-    hipLaunchKernelGGL((k_gemm_x3<EPI_BIAS, NT>), grid, block, 0, st, M, Kp, nnt, W, ws, X, ldx, X2, ldx2, nk1, OUT,
-                       ldc, bias, aux, ldaux, os, as, 0);
-  else if (epi == EPI_BIAS_ELU)
-    hipLaunchKernelGGL((k_gemm_x3<EPI_BIAS_ELU, NT>), grid, block, 0, st, M, Kp, nnt, W, ws, X, ldx, X2, ldx2, nk1,
-                       OUT, ldc, bias, aux, ldaux, os, as, 0);
-  else
-    hipLaunchKernelGGL((k_gemm_x3<EPI_DELU, NT>), grid, block, 0, st, M, Kp, nnt, W, ws, X, ldx, X2, ldx2, nk1, OUT,
-                       ldc, bias, aux, ldaux, os, as, x3_stage_aux());
+  with_epi(epi, [&](auto e) {  // only the DELU epilogue has operands to stage
+    constexpr int E = decltype(e)::value;
+    hipLaunchKernelGGL((k_gemm_x3<E, NT>), grid, block, 0, st, M, Kp, nnt, W, ws, X, ldx, X2, ldx2, nk1, OUT, ldc, bias,
+                       aux, ldaux, os, as, E == EPI_DELU ? x3_stage_aux() : 0);
+  });
 }
 // ws: the weight matrix's scale 2^-s (pack_split_x3) with the operand exponents folded in; os / as:
 // the ELU output's store scale / the DELU operand's read scale (dpi_gemm.h).  X2 != nullptr: K
@@ -1388,10 +1385,7 @@ static void gemm_x3(int epi, int M, int Kp, int Np, const uint32_t* W, float ws,
 
 // k_pis_net (the fused split VJP chain) by default; DPI_PIS_FUSED=0 selects the layer-wise
 // k_gemm_x3h chain (read per call, so one process can compare both).
-static bool pis_fused_on() {
-  const char* e = std::getenv("DPI_PIS_FUSED");
-  return !e || std::atoi(e) != 0;
-}
+static bool pis_fused_on() { return env_int("DPI_PIS_FUSED", 1) != 0; }
 // k_pis_net's shapes: 1-4 hidden layers of 512 units, nx <= 128 (X in <= 4 chunks, GX 64 or 128 wide)
 static bool pis_fused_fits(const NetPisDev& pd, const PisRows& L) {
   if (pd.L < 1 || pd.L > 4) return false;
@@ -1417,8 +1411,8 @@ static PisRows pis_chain_x3(const NetPisDev& pd, float* rows, int R, hipStream_t
   if (vjp && R > 0 && pis_fused_on() && pis_fused_fits(pd, L)) {
     const dim3 grid((R + PN_BM - 1) / PN_BM), block(PN_THREADS);
     // DPI_PIS_NT: 2 (default) non-temporal row loads, plain stores; 1 both non-temporal; 0 neither
-    const char* e = std::getenv("DPI_PIS_NT");
-    const int ntm = e ? (std::atoi(e) == 1 ? 3 : std::atoi(e) == 0 ? 0 : 1) : 1;
+    const int nt = env_int("DPI_PIS_NT", 2);
+    const int ntm = nt == 1 ? 3 : nt == 0 ? 0 : 1;
     hipEvent_t t0, t1;
     take_timer(t0, t1);
     auto launch = [&](auto ntc, auto nlc) {
@@ -1574,53 +1568,44 @@ extern "C" int dpi_sample_points_t(dpi_problem p, int n, uint64_t seed, uint32_t
 }
 
 static bool dispatch_any(const dpi_problem_s* p, const dpi_net_s* net, const Launch& q) {
-  if (q.fbase) {  // k_paths_fb (fused_base_ok)
-    switch (p->e.kind) {
-      case DPI_EQ_CHA:
-        return dispatch_fb_cha(p, net, q);
-      case DPI_EQ_OU:
-        return dispatch_fb_ou(p, net, q);
-      default:
-        return false;
-    }
-  }
-  const bool td = q.td && !q.baseline && !q.hess;
-  if (p->e.nx > NXP_MAX && !q.baseline) {  // the wide first-order units (nx <= NXW_MAX; Cha / OU)
-    if (td || q.hess) return false;
-    const bool tanh = net->d.kind == 1 && net->d.act == DPI_ACT_TANH;
-    switch (p->e.kind) {
-      case DPI_EQ_CHA:
-        return tanh ? dispatch_wide_cha_tanh(p, net, q) : dispatch_wide_cha(p, net, q);
-      case DPI_EQ_OU:
-        return tanh ? dispatch_wide_ou_tanh(p, net, q) : dispatch_wide_ou(p, net, q);
-      case DPI_EQ_GBM:
-        return tanh ? dispatch_wide_gbm_tanh(p, net, q) : dispatch_wide_gbm(p, net, q);
-      default:
-        return false;
-    }
-  }
-  if (net->d.kind == 1 && net->d.act == DPI_ACT_TANH && !q.baseline) {  // the Tanh k_paths units
-    switch (p->e.kind) {
-      case DPI_EQ_CHA:
-        return td ? dispatch_td_cha_tanh(p, net, q) : dispatch_cha_tanh(p, net, q);
-      case DPI_EQ_OU:
-        return td ? dispatch_td_ou_tanh(p, net, q) : dispatch_ou_tanh(p, net, q);
-      case DPI_EQ_GBM:
-        return td ? dispatch_td_gbm_tanh(p, net, q) : dispatch_gbm_tanh(p, net, q);
-      default:
-        return false;
-    }
-  }
-  switch (p->e.kind) {
-    case DPI_EQ_CHA:
-      return td ? dispatch_td_cha(p, net, q) : dispatch_cha(p, net, q);
-    case DPI_EQ_OU:
-      return td ? dispatch_td_ou(p, net, q) : dispatch_ou(p, net, q);
-    case DPI_EQ_GBM:
-      return td ? dispatch_td_gbm(p, net, q) : dispatch_gbm(p, net, q);
-    default:
-      return false;
-  }
+  // The unit's key (dpi_dispatch.h DPI_UNITS).  k_paths_fb (fused_base_ok) has ELU, non-TD, narrow
+  // rows only, and GBM has none.  The baseline is shape- and activation-generic: it lives in the
+  // plain ELU units whatever the net's activation, the problem's width or TD mode.  The wide
+  // first-order units (nx <= NXW_MAX) have no TD or Hessian forms.
+  const bool fb = q.fbase != nullptr, paths = !q.baseline && !fb;
+  const bool td = paths && q.td && !q.hess;
+  const bool wide = paths && p->e.nx > NXP_MAX;
+  if (wide && (td || q.hess)) return false;
+  const bool tanh = paths && net->d.kind == 1 && net->d.act == DPI_ACT_TANH;
+  const int act = tanh ? DPI_ACT_TANH : DPI_ACT_ELU, nxw = wide ? NXW_MAX : NXP_MAX;
+  for (const Unit& u : UNITS)
+    if (u.is(p->e.kind, td, act, fb, nxw)) return u.dispatch(p, net, q);
+  return false;  // no such unit: GBM has no fused baseline
+}
+
+// The two kinds of Launch.  The per-point baseline of n points writes the workspace's gx / fb / bx /
+// hb regions and zeroes the fused reduce's tickets; a path launch (k_paths, k_paths_fb) runs nblocks
+// workgroups over a's paths.
+static Launch baseline_launch(const float* tx, int n, void* ws, const WsLayout& w, hipStream_t st) {
+  char* b = (char*)ws;
+  Launch q;
+  q.baseline = true;
+  q.tx = tx;
+  q.n = n;
+  q.gx = (float*)(b + w.gx);
+  q.fb = (float*)(b + w.fb);
+  q.bx = (float*)(b + w.bx);
+  q.hb = (float*)(b + w.hb);
+  q.tickets = (int*)(b + w.tk);
+  q.st = st;
+  return q;
+}
+static Launch path_launch(const PathArgs& a, int nblocks, hipStream_t st) {
+  Launch q;
+  q.a = &a;
+  q.nblocks = nblocks;
+  q.st = st;
+  return q;
 }
 
 static int check_pair(dpi_problem p, dpi_net net);
@@ -1649,11 +1634,7 @@ static int pis_baseline(dpi_problem p) { return pis_check(p); }
 // Independent Philox chains per wave in the PISGradNet rollout: 4 (default; 61 VGPRs) or 2
 // (DPI_PIS_UNROLL=2; 47 VGPRs, room beside the 256 x 128 GEMM's blocks).
 static int pis_rollout_unroll() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = std::getenv("DPI_PIS_UNROLL");
-    v = (e && std::atoi(e) == 2) ? 2 : 4;
-  }
+  static const int v = env_int("DPI_PIS_UNROLL", 4) == 2 ? 2 : 4;
   return v;
 }
 
@@ -1661,22 +1642,14 @@ static int pis_rollout_unroll() {
 // Round 3's k_gemm_x3 chain needed bounded grids (3 per CU) so the rollout did not pack whole CUs;
 // the one-wave rollout beside k_pis_net runs as one grid by default.
 static int pis_prep_per_cu() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = std::getenv("DPI_PIS_PREP_PER_CU");
-    v = e ? std::max(0, std::min(64, std::atoi(e))) : 0;
-  }
+  static const int v = env_int("DPI_PIS_PREP_PER_CU", 0, 0, 64);
   return v;
 }
 
 // The prepare stream's rollout as the per-SIMD-capped work queue (k_pis_rollout_shared), launched
 // with DPI_PIS_PREP_SHARED (default 2) waves per SIMD more than it keeps; 0: the plain grid.
 static int pis_prep_shared() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = std::getenv("DPI_PIS_PREP_SHARED");
-    v = e ? std::max(0, std::min(8, std::atoi(e))) : 2;
-  }
+  static const int v = env_int("DPI_PIS_PREP_SHARED", 2, 0, 8);
   return v;
 }
 
@@ -1687,11 +1660,7 @@ static int pis_prep_shared() {
 // boxes (profiles/r06x, r06y; 60 steps, two runs each): f = 0.88 3.738 / 3.752 and 3.798 / 3.806
 // ms/step against 0.92's 3.763 / 3.774 and 3.831 / 3.827 (0.82: 3.797 / 3.810; 0.96, 1.0, 0.76 slower).
 static int pis_prep_sets(int g) {
-  static double f = -1.0;
-  if (f < 0.0) {
-    const char* e = std::getenv("DPI_PIS_PREP_FRAC");
-    f = e ? std::max(0.0, std::min(1.0, std::atof(e))) : 0.88;
-  }
+  static const double f = env_real("DPI_PIS_PREP_FRAC", 0.88, 0.0, 1.0);
   return std::max(0, std::min(g, (int)(f * g + 0.5)));
 }
 
@@ -1813,11 +1782,8 @@ int dpi_point_baseline(dpi_problem p, dpi_net net, const float* tx, int n, void*
   if (n == 0) return 0;
   const WsLayout w = ws_layout(net, n, 0, 1 + p->e.nx);
   if (ws_bytes < w.partial) return fail(DPI_ERR_WORKSPACE, "workspace too small");
-  char* b = (char*)ws;
   if (net->d.kind == 2) return pis_baseline(p);
-  Launch q{true, tx, n, (float*)(b + w.gx), (float*)(b + w.fb), (float*)(b + w.bx), (float*)(b + w.hb), nullptr, 0,
-           (hipStream_t)stream};
-  q.tickets = (int*)(b + w.tk);
+  const Launch q = baseline_launch(tx, n, ws, w, (hipStream_t)stream);
   if (!dispatch_any(p, net, q)) return fail(DPI_ERR_UNSUPPORTED, "point_baseline: unsupported equation/network shape");
   HIPCHK(hipGetLastError());
   base_tag_set(ws, n);
@@ -1825,37 +1791,49 @@ int dpi_point_baseline(dpi_problem p, dpi_net net, const float* tx, int n, void*
 }
 
 // The label reduce inside k_paths (fused_reduce) for first-order labels with <= 64 path blocks per
-// point: one launch fewer per label call.  DPI_FUSED_REDUCE=0 keeps the separate k_reduce launch.
-static bool fused_reduce_on() {  // read per call, so one process can compare both
-  const char* e = std::getenv("DPI_FUSED_REDUCE");
-  return !e || std::atoi(e) != 0;
-}
+// point: one launch fewer per label call.  DPI_FUSED_REDUCE=0 keeps the separate k_reduce launch
+// (read per call, so one process can compare both).
+static bool fused_reduce_on() { return env_int("DPI_FUSED_REDUCE", 1) != 0; }
 
 // k_paths phase order policy (see the kernel); DPI_ORDER overrides for ablations.
-static int path_order() {
-  const char* e = std::getenv("DPI_ORDER");
-  return e ? std::atoi(e) : 0;
-}
+static int path_order() { return env_int("DPI_ORDER", 0); }
 
-// Validates a label-moments call and fills its PathArgs (shared by dpi_label_moments and
-// dpi_label_prepare).  Returns 0, or the error; *w receives the workspace layout.
+static size_t hess_extra(int n, int M, int nx, size_t* moff);
+// Validates a label-moments call and fills its PathArgs (shared by dpi_label_moments,
+// dpi_label_prepare and, with `hess`, the Hessian-label calls: GBM with MLP or zero nets only, their
+// own error texts, and the Hessian block sums and moments behind the layout, hess_extra).  Returns
+// 0, or the error; *w receives the workspace layout.
 static int label_args(dpi_problem p, dpi_net net, const float* tx, int n, int M, int K, uint64_t seed,
                       uint32_t epoch, uint32_t point_base, int m_begin, int m_end, int flags, bool need_moments,
-                      const float* moments, void* ws, size_t ws_bytes, WsLayout* w, PathArgs* pa) {
+                      const float* moments, void* ws, size_t ws_bytes, WsLayout* w, PathArgs* pa, bool hess = false) {
   const bool prepared = !need_moments || (flags & DPI_PREPARED);  // dpi_label_prepare, or its prepared call
   int rc = check_pair(p, net);
   if (rc) return rc;
+  if (hess && p->e.kind != DPI_EQ_GBM)
+    return fail(DPI_ERR_UNSUPPORTED, "Hessian labels need a SimpleDiffusionEquationWithHessian (GBMEquationComplexExact)");
+  if (hess && net->d.kind == 2) return fail(DPI_ERR_UNSUPPORTED, "Hessian labels: MLP or ZeroSolution networks only");
   if (n < 0 || (n && (!tx || !ws || (need_moments && !moments))) || K < 1 || M < 1 || m_begin < 0 || m_end > M ||
       m_end <= m_begin || (m_begin % P) || (m_end % P) || !(flags & DPI_BOTH) || (flags & ~(DPI_BOTH | DPI_PREPARED)) ||
       epoch > 0xFFFFFFu)
-    return fail(DPI_ERR_ARG, "label_moments: bad arguments (m range multiple of 64 within [0, M], K >= 1)");
+    return fail(DPI_ERR_ARG,
+                hess ? "Hessian labels: bad arguments (m range multiple of 64 within [0, M], K >= 1, flags in "
+                       "DPI_TERMINAL | DPI_INTEGRAL | DPI_PREPARED)"
+                     : "label_moments: bad arguments (m range multiple of 64 within [0, M], K >= 1)");
   if (n == 0) return 0;
   const int F = 1 + p->e.nx;
   const int nbp = (m_end - m_begin) / P;
-  if (nbp > DPI_PATHS_PER_CALL_MAX / P) return fail(DPI_ERR_ARG, "label_moments: at most DPI_PATHS_PER_CALL_MAX paths per call");
+  if (nbp > DPI_PATHS_PER_CALL_MAX / P)
+    return fail(DPI_ERR_ARG, std::string(hess ? "Hessian labels" : "label_moments") +
+                                 ": at most DPI_PATHS_PER_CALL_MAX paths per call");
   // the noise staging region only for dpi_label_prepare and the DPI_PREPARED call it feeds
-  *w = ws_layout(net, n, M, F, prepared && gbm_noise_prep(p, net));
-  if (ws_bytes < w->total)
+  const bool noise = prepared && gbm_noise_prep(p, net);
+  *w = ws_layout(net, n, M, F, noise);
+  if (hess) {
+    size_t moff;
+    if (ws_bytes < al256(w->total) + hess_extra(n, M, p->e.nx, &moff))
+      return fail(DPI_ERR_WORKSPACE, noise ? "workspace too small (dpi_workspace_bytes_hessians_prepared)"
+                                           : "workspace too small (dpi_workspace_bytes_hessians)");
+  } else if (ws_bytes < w->total)
     return fail(DPI_ERR_WORKSPACE, prepared ? "workspace too small (prepared calls: dpi_workspace_bytes_prepared)"
                                             : "workspace too small");
   char* b = (char*)ws;
@@ -1885,6 +1863,19 @@ static int label_args(dpi_problem p, dpi_net net, const float* tx, int n, int M,
   return 0;
 }
 
+// Arms the fused reduce of a path launch: k_paths' last block per point counts on the workspace's
+// tickets, reduces the point's partials into `moments` and finalizes the labels into y.
+static void arm_fused_reduce(PathArgs& a, dpi_net net, void* ws, const WsLayout& w, int M, int flags, float* moments,
+                             float* y, float bound) {
+  a.tickets = (int*)((char*)ws + w.tk);
+  a.rd_moments = moments;
+  a.rd_y = y;
+  a.rd_status = net_status(net);
+  a.rd_invM = 1.0f / (float)M;
+  a.rd_bound = bound;
+  a.rd_add_g = (flags & DPI_TERMINAL) ? 1 : 0;
+}
+
 static bool stages_prepare(dpi_problem p, dpi_net net);
 static int moments_impl(dpi_problem p, dpi_net net, const float* tx, int n, int M, int K, uint64_t seed,
                         uint32_t epoch, uint32_t point_base, int m_begin, int m_end, int flags, float* moments,
@@ -1901,7 +1892,7 @@ static int moments_impl(dpi_problem p, dpi_net net, const float* tx, int n, int 
   if (net->d.kind == 2) {
     if ((rc = pis_paths(p, net, tx, n, K, a, w, b, st, (flags & DPI_PREPARED) != 0))) return rc;
   } else {
-    Launch q{false, nullptr, 0, nullptr, nullptr, nullptr, nullptr, &a, n * nbp, st};
+    Launch q = path_launch(a, n * nbp, st);
     q.td = p->td_dt > 0.f;
     if (q.td && p->e.nx > NXP_MAX)
       return fail(DPI_ERR_UNSUPPORTED, "label_moments: the TD estimators (ESTIMATE_DELTA_T > 0) are compiled for "
@@ -1912,13 +1903,7 @@ static int moments_impl(dpi_problem p, dpi_net net, const float* tx, int n, int 
       if (!base_tag_ok(ws, n))
         return fail(DPI_ERR_ARG, "label_moments: no dpi_point_baseline / dpi_sample_points_baseline of these n points "
                                  "was enqueued on this workspace (the fused reduce's tickets are zeroed there)");
-      a.tickets = (int*)(b + w.tk);
-      a.rd_moments = moments;
-      a.rd_y = y;
-      a.rd_status = net_status(net);
-      a.rd_invM = 1.0f / (float)M;
-      a.rd_bound = bound;
-      a.rd_add_g = (flags & DPI_TERMINAL) ? 1 : 0;
+      arm_fused_reduce(a, net, ws, w, M, flags, moments, y, bound);
     }
     if (!dispatch_any(p, net, q))
       return fail(DPI_ERR_UNSUPPORTED, "label_moments: unsupported equation/network shape");
@@ -1936,19 +1921,15 @@ static int moments_impl(dpi_problem p, dpi_net net, const float* tx, int n, int 
 }
 
 // The one-launch dpi_sample_with_gradients (DPI_FUSED_BASE=0: two launches; read per call).
-static bool fused_base_on() {
-  const char* e = std::getenv("DPI_FUSED_BASE");
-  return !e || std::atoi(e) != 0;
-}
-// The nets and problems k_paths_fb is instantiated for (dpi_dispatch.h fused_base_shape):
-// first-order Cha / OU labels without TD, of zero nets or ELU MLP nets in the fp16-split mode
-// (H % 32 == 0, the fused-MLP instances; not OU 4 x 128); the rest runs the two-launch form.
+static bool fused_base_on() { return env_int("DPI_FUSED_BASE", 1) != 0; }
+// The nets and problems k_paths_fb is instantiated for (dpi_dispatch.h fused_base_shape, the one
+// predicate do_launch instantiates by): first-order Cha / OU labels of zero nets or ELU MLP nets
+// (H % 32 == 0, the fused-MLP instances; not OU 4 x 128).  The run-time conditions on top: no TD,
+// nx <= NXP_MAX, and MLP nets in the fp16-split mode; the rest runs the two-launch form.
 static bool fused_base_ok(dpi_problem p, dpi_net net) {
-  if (p->e.kind == DPI_EQ_GBM || p->td_dt > 0.f || p->e.nx > NXP_MAX) return false;
-  if (net->d.kind == 0) return true;
-  const int H = net->d.H, L = net->d.L;
-  return net->d.kind == 1 && net->d.act == DPI_ACT_ELU && H % 32 == 0 && mlp_split(net) &&
-         !(p->e.kind == DPI_EQ_OU && H == 128 && L == 4);
+  if (p->td_dt > 0.f || p->e.nx > NXP_MAX) return false;
+  if (net->d.kind == 0) return fused_base_shape(p->e.kind, 0, 0, true, DPI_ACT_ELU);
+  return net->d.kind == 1 && mlp_split(net) && fused_base_shape(p->e.kind, net->d.H, net->d.L, false, net->d.act);
 }
 // Hand-off sequence numbers: one per fused launch, process-wide, never 0, so a hand-off word left
 // in a workspace by an earlier launch (or never written) does not match this launch's.
@@ -1992,20 +1973,14 @@ int dpi_sample_with_gradients(dpi_problem p, dpi_net net, int n, int M, int K, u
                          &a)))
       return rc;
     char* b = (char*)ws;
-    a.tickets = (int*)(b + wl.tk);
-    a.rd_moments = moments;
-    a.rd_y = y;
-    a.rd_status = net_status(net);
-    a.rd_invM = 1.0f / (float)M;
-    a.rd_bound = sample_bound;
-    a.rd_add_g = (flags & DPI_TERMINAL) ? 1 : 0;
+    arm_fused_reduce(a, net, ws, wl, M, flags, moments, y, sample_bound);
     FusedBase fb{};
     fb.nbase = n;
     fb.rec = (float*)(b + wl.rec);
     fb.ready = (unsigned long long*)(b + wl.ready);
     fb.ready_seq = next_ready_seq();
     fb.smp = sample_spec(p, seed, epoch, point_base, eps, t_factors, tx);
-    Launch q{false, nullptr, 0, nullptr, nullptr, nullptr, nullptr, &a, n + n * a.nbp, (hipStream_t)stream};
+    Launch q = path_launch(a, n + n * a.nbp, (hipStream_t)stream);
     q.fbase = &fb;
     take_timer(q.t0, q.t1);
     if (!dispatch_any(p, net, q))
@@ -2035,11 +2010,8 @@ int dpi_sample_points_baseline(dpi_problem p, dpi_net net, int n, uint64_t seed,
   }
   const WsLayout w = ws_layout(net, n, 0, 1 + p->e.nx);
   if (ws_bytes < w.partial) return fail(DPI_ERR_WORKSPACE, "workspace too small");
-  char* b = (char*)ws;
-  Launch q{true, tx, n, (float*)(b + w.gx), (float*)(b + w.fb), (float*)(b + w.bx), (float*)(b + w.hb), nullptr, 0,
-           (hipStream_t)stream};
+  Launch q = baseline_launch(tx, n, ws, w, (hipStream_t)stream);
   q.smp = sample_spec(p, seed, epoch, point_base, eps, t_factors, tx);
-  q.tickets = (int*)(b + w.tk);
   if (!dispatch_any(p, net, q))
     return fail(DPI_ERR_UNSUPPORTED, "sample_points_baseline: unsupported equation/network shape");
   HIPCHK(hipGetLastError());
@@ -2245,59 +2217,29 @@ size_t dpi_workspace_bytes_hessians_prepared(dpi_problem p, dpi_net net, int n, 
 static int hess_moments_impl(dpi_problem p, dpi_net net, const float* tx, int n, int M, int K, uint64_t seed,
                              uint32_t epoch, uint32_t point_base, int m_begin, int m_end, int flags, float* moments,
                              float* hsum, void* ws, size_t ws_bytes, void* stream, float* y, float bound) {
-  int rc = check_pair(p, net);
-  if (rc) return rc;
-  if (p->e.kind != DPI_EQ_GBM)
-    return fail(DPI_ERR_UNSUPPORTED, "Hessian labels need a SimpleDiffusionEquationWithHessian (GBMEquationComplexExact)");
-  if (net->d.kind == 2) return fail(DPI_ERR_UNSUPPORTED, "Hessian labels: MLP or ZeroSolution networks only");
-  if (n < 0 || (n && (!tx || !ws || !moments)) || K < 1 || M < 1 || m_begin < 0 || m_end > M || m_end <= m_begin ||
-      (m_begin % P) || (m_end % P) || epoch > 0xFFFFFFu || !(flags & DPI_BOTH) || (flags & ~(DPI_BOTH | DPI_PREPARED)))
-    return fail(DPI_ERR_ARG, "Hessian labels: bad arguments (m range multiple of 64 within [0, M], K >= 1, flags in "
-                             "DPI_TERMINAL | DPI_INTEGRAL | DPI_PREPARED)");
-  if (n == 0) return 0;
-  const int nx = p->e.nx, F = 1 + nx, C = nx * nx, nbp = (m_end - m_begin) / P;
-  if (nbp > DPI_PATHS_PER_CALL_MAX / P) return fail(DPI_ERR_ARG, "Hessian labels: at most DPI_PATHS_PER_CALL_MAX paths per call");
+  // The shared validation and PathArgs fill; a.split selects the fp16-split tangent sweeps
+  // (mlp_hdiag_split) unless DPI_GEMM_F32.  label_args also sets a.order (DPI_ORDER) and a.td_dt,
+  // which the Hessian-label launch ignores: k_paths reads a.order only in its non-GBM, non-split
+  // instances and a.td_dt only under TD, and the Hessian instances are GBM and non-TD.
+  WsLayout w;
+  PathArgs a;
+  int rc = label_args(p, net, tx, n, M, K, seed, epoch, point_base, m_begin, m_end, flags, true, moments, ws, ws_bytes,
+                      &w, &a, true);
+  if (rc || n == 0) return rc;
+  const int nx = p->e.nx, F = 1 + nx, C = nx * nx, nbp = a.nbp;
+  char* b = (char*)ws;
   // a prepared call (GBM): the terminal / integral noise sums were staged by dpi_label_prepare's
   // k_noise_shared in the prepared layout's noise region — the same counters and summation order as
   // the path launch's own rollout, so the labels are bitwise the unprepared call's
-  const bool staged = (flags & DPI_PREPARED) && gbm_noise_prep(p, net);
-  const WsLayout w = ws_layout(net, n, M, F, staged);
-  size_t moff;
-  const size_t base = al256(w.total), need = base + hess_extra(n, M, nx, &moff);
-  if (ws_bytes < need)
-    return fail(DPI_ERR_WORKSPACE, staged ? "workspace too small (dpi_workspace_bytes_hessians_prepared)"
-                                          : "workspace too small (dpi_workspace_bytes_hessians)");
-  char* b = (char*)ws;
-  PathArgs a;
-  std::memset(&a, 0, sizeof(a));
-  a.tx = tx;
-  a.gx = (const float*)(b + w.gx);
-  a.fb = (const float*)(b + w.fb);
-  a.bx = (const float*)(b + w.bx);
-  a.hb = (const float*)(b + w.hb);
-  a.partial = (float*)(b + w.partial);
-  a.n = n;
-  a.nbp = nbp;
-  a.m_begin = m_begin;
-  a.K = K;
-  a.flags = flags & DPI_BOTH;
-  if (staged) a.noise = (const float*)(b + w.noise);
-  a.k0 = (uint32_t)seed;
-  a.k1 = (uint32_t)(seed >> 32);
-  a.c3t = DPI_TAG_TERM | (epoch << 8);
-  a.c3s = DPI_TAG_S | (epoch << 8);
-  a.c3i = DPI_TAG_INT | (epoch << 8);
-  a.c3q = DPI_TAG_SDGD | (epoch << 8);
+  if ((flags & DPI_PREPARED) && gbm_noise_prep(p, net)) a.noise = (const float*)(b + w.noise);
   a.c3h1 = DPI_TAG_HTERM | (epoch << 8);
   a.c3h2 = DPI_TAG_HINT | (epoch << 8);
-  a.split = mlp_split(net) ? 1 : 0;  // fp16-split tangent sweeps (mlp_hdiag_split) unless DPI_GEMM_F32
-  a.point_base = point_base;
-  a.hpart = (float*)(b + base);
+  a.hpart = (float*)(b + al256(w.total));  // [packed block sums | moments] behind the layout (hess_extra)
   const int NT = (nx + 15) / 16;
   hipStream_t st = (hipStream_t)stream;
   if (p->e.nx > NXP_MAX)
     return fail(DPI_ERR_UNSUPPORTED, "Hessian labels: compiled for nx <= 128 (NXP_MAX)");
-  Launch q{false, nullptr, 0, nullptr, nullptr, nullptr, nullptr, &a, n * nbp, st};
+  Launch q = path_launch(a, n * nbp, st);
   q.hess = true;
   take_timer(q.t0, q.t1);
   if (!dispatch_any(p, net, q))

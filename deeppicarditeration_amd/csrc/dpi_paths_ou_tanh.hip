@@ -2,7 +2,4 @@
 // reference's default NETWORK.ACTIVATIONS, picard/config.py:61); the TD estimators in
 // dpi_paths_td_ou_tanh.hip.
 #include "dpi_dispatch.h"
-
-bool dispatch_ou_tanh(const dpi_problem_s* p, const dpi_net_s* net, const Launch& q) {
-  return dpi_dispatch<DPI_EQ_OU, false, DPI_ACT_TANH>(p, net, q);
-}
+DPI_UNIT_DEFINE(ou_tanh)

@@ -1812,7 +1812,10 @@ struct PathArgs {
   const float* bx;
   const float* hb;  // GBM: baseline Hessian diagonal [n][HBS]
   float* partial;
-  int n, nbp, m_begin, K, flags;
+  // MC indices [m_begin, m_end) of the call: m_begin a multiple of 64; m_end a multiple of 64 or the
+  // sample count M, and then the lanes m >= m_end of the last block are dead: they roll out and
+  // evaluate like any other (legal counters, finite values) and add exactly +0 to every sum
+  int n, nbp, m_begin, m_end, K, flags;
   uint32_t k0, k1, c3t, c3s, c3i, c3q, point_base;
   int order;  // phase order policy (k_paths)
   int split;  // fused MLP on the fp16-split MFMA
@@ -2041,6 +2044,9 @@ __device__ __forceinline__ void hess_block(const EqDev& e, const NetDev& net, co
   // sample counts (data.py:845 vs :1164), each with its own identity part
   const bool TERM = a.flags & DPI_TERMINAL, INTG = a.flags & DPI_INTEGRAL;
   float aI = 0.f, aT = 0.f;
+  // live paths of this block (>= 64: all); a dead path (PathArgs::m_end) weighs +0, by select, in
+  // the outer products and in the identity part
+  const int nlive = a.m_end - a.m_begin - P * blk;
 
   // ---- integral term: N2 -> noise tile, w . N2 for the exact-solution terms
   __syncthreads();  // phase 3 is done with the integral noise tile
@@ -2082,7 +2088,8 @@ __device__ __forceinline__ void hess_block(const EqDev& e, const NetDev& net, co
   __syncthreads();
   const float fminus = f_eval();
   const float fbp = sh.fbp[pp];
-  if (qq == 0) wgt[pp] = tmt * ((fplus + fminus - 2.f * fbp) * 0.5f / sh.smt[pp]);  // path pp, not this lane's
+  // path pp, not this lane's
+  if (qq == 0) wgt[pp] = pp < nlive ? tmt * ((fplus + fminus - 2.f * fbp) * 0.5f / sh.smt[pp]) : 0.f;
   __syncthreads();
   aI = wgt[lane];  // lane = path
   hess_accum<H, L>(sh, wgt, NT, acc);
@@ -2126,7 +2133,7 @@ __device__ __forceinline__ void hess_block(const EqDev& e, const NetDev& net, co
   };
   const float gplus = wave_stats(gp);
   const float gminus = wave_stats(gm);
-  aT = (gplus + gminus - 2.f * g_x) * 0.5f / tmt;
+  aT = lane < nlive ? (gplus + gminus - 2.f * g_x) * 0.5f / tmt : 0.f;  // lane = path; dead: +0
   if (wv == 0) wgt[lane] = aT;
   __syncthreads();
   hess_accum<H, L>(sh, wgt, NT, acc);
@@ -2635,6 +2642,17 @@ __device__ __forceinline__ void paths_body(const EqDev& e, const NetDev& net, co
   }
 
   // ---------------- phase 3: per-path contributions -> per-block partial slab
+  // dead lanes (m >= a.m_end, the last block of a count that is no multiple of 64): a_p, b_p's two
+  // uses and the baseline term of the value column are selected to +0 here, so every column below is
+  // +0 for them whatever they computed; all lanes live: the selects are the identity.  b_p is
+  // selected where it is used, not at its LDS read (that form left the zero-net k_paths_fb instance
+  // with a stack object).  The mask is m < m_end; the split OU 4 x 128 instance, at 255 registers,
+  // spilled three with it and compares the lane with the block's live-lane count, formed from
+  // scalars, instead (the same predicate: m = m_begin + 64 blk + lane) — a form that slowed the
+  // Burgers launch, so only there
+  constexpr bool MASK_SCALAR = KIND == DPI_EQ_OU && H == 128 && L == 4 && SPLIT && !TD && NXW == NXP_MAX;
+  const bool live = MASK_SCALAR ? lane < a.m_end - a.m_begin - P * blk : m < (uint32_t)a.m_end;
+  ap = live ? ap : 0.f;
   const float bp = sh.bsh[lane];
   // partial slab layout [point][block][slab_row(F)]: this workgroup's 2F sums are one contiguous,
   // 128-B aligned row, so every HBM line of the slab is written from a single XCD (a column-major
@@ -2643,7 +2661,7 @@ __device__ __forceinline__ void paths_body(const EqDev& e, const NetDev& net, co
   float* out = a.partial + ((size_t)i * a.nbp + blk) * slab_row(F);
   // per-block sums of c and c^2 for this wave's columns: 2 per owned dim (d = 4 (wv + 4c) + q,
   // column 8c + 2q + {0: sum, 1: sum of squares}) and, on wave 0, the value column (56, 57)
-  const float aY = ap * yT, bY = bp * yI;
+  const float aY = ap * yT, bY = live ? bp * yI : 0.f;
   if constexpr (NXW == NXP_MAX) {
     float col[64];
   #pragma unroll
@@ -2667,7 +2685,7 @@ __device__ __forceinline__ void paths_body(const EqDev& e, const NetDev& net, co
         fbt = sh.fbp[lane];
       else
         fbt = f_b + Eq<KIND>::ffc(e);
-      const float c0 = ap + bp + (INTG ? fbt * tmt : 0.f);
+      const float c0 = ap + (live ? bp : 0.f) + (INTG ? (live ? fbt : 0.f) * tmt : 0.f);
       col[56] = c0;
       col[57] = c0 * c0;
     }
@@ -2722,7 +2740,7 @@ __device__ __forceinline__ void paths_body(const EqDev& e, const NetDev& net, co
           fbt = sh.fbp[lane];
         else
           fbt = f_b + Eq<KIND>::ffc(e);
-        const float c0 = ap + bp + (INTG ? fbt * tmt : 0.f);
+        const float c0 = ap + (live ? bp : 0.f) + (INTG ? (live ? fbt : 0.f) * tmt : 0.f);
         col[56] = c0;
         col[57] = c0 * c0;
       }

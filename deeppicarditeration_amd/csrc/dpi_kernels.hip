@@ -1740,8 +1740,8 @@ static int pis_paths(dpi_problem p, dpi_net net, const float* tx, int n, int K, 
     if (base)
       hipLaunchKernelGGL((k_pis_base_final<DPI_EQ_OU, X3>), dim3((n + 63) / 64), dim3(256), 0, st, p->e, net->pis,
                          tx, brows, Lc, n, fb, (float*)(b + w.gx));
-    hipLaunchKernelGGL((k_pis_final<DPI_EQ_OU, X3>), dim3(g), dim3(NTH), 0, st, p->e, net->pis, tx, g0, a.nbp, K,
-                       a.flags, fb, a.gx, rows, Lc, a.partial, dt);
+    hipLaunchKernelGGL((k_pis_final<DPI_EQ_OU, X3>), dim3(g), dim3(NTH), 0, st, p->e, net->pis, tx, g0, a.nbp,
+                       a.m_begin, a.m_end, K, a.flags, fb, a.gx, rows, Lc, a.partial, dt);
   };
   for (int g0 = 0; g0 < G; g0 += GC) {
     const int g = std::min(GC, G - g0);
@@ -1813,15 +1813,17 @@ static int label_args(dpi_problem p, dpi_net net, const float* tx, int n, int M,
     return fail(DPI_ERR_UNSUPPORTED, "Hessian labels need a SimpleDiffusionEquationWithHessian (GBMEquationComplexExact)");
   if (hess && net->d.kind == 2) return fail(DPI_ERR_UNSUPPORTED, "Hessian labels: MLP or ZeroSolution networks only");
   if (n < 0 || (n && (!tx || !ws || (need_moments && !moments))) || K < 1 || M < 1 || m_begin < 0 || m_end > M ||
-      m_end <= m_begin || (m_begin % P) || (m_end % P) || !(flags & DPI_BOTH) || (flags & ~(DPI_BOTH | DPI_PREPARED)) ||
-      epoch > 0xFFFFFFu)
+      m_end <= m_begin || (m_begin % P) || ((m_end % P) && m_end != M) || !(flags & DPI_BOTH) ||
+      (flags & ~(DPI_BOTH | DPI_PREPARED)) || epoch > 0xFFFFFFu)
     return fail(DPI_ERR_ARG,
-                hess ? "Hessian labels: bad arguments (m range multiple of 64 within [0, M], K >= 1, flags in "
-                       "DPI_TERMINAL | DPI_INTEGRAL | DPI_PREPARED)"
-                     : "label_moments: bad arguments (m range multiple of 64 within [0, M], K >= 1)");
+                hess ? "Hessian labels: bad arguments (m range within [0, M], m_begin a multiple of 64, m_end a "
+                       "multiple of 64 or M; K >= 1, flags in DPI_TERMINAL | DPI_INTEGRAL | DPI_PREPARED)"
+                     : "label_moments: bad arguments (m range within [0, M], m_begin a multiple of 64, m_end a "
+                       "multiple of 64 or M; K >= 1)");
   if (n == 0) return 0;
   const int F = 1 + p->e.nx;
-  const int nbp = (m_end - m_begin) / P;
+  // whole 64-path blocks; the lanes of the last one at m >= m_end are dead (PathArgs::m_end)
+  const int nbp = (m_end - m_begin + P - 1) / P;
   if (nbp > DPI_PATHS_PER_CALL_MAX / P)
     return fail(DPI_ERR_ARG, std::string(hess ? "Hessian labels" : "label_moments") +
                                  ": at most DPI_PATHS_PER_CALL_MAX paths per call");
@@ -1848,6 +1850,7 @@ static int label_args(dpi_problem p, dpi_net net, const float* tx, int n, int M,
   a.n = n;
   a.nbp = nbp;
   a.m_begin = m_begin;
+  a.m_end = m_end;
   a.K = K;
   a.flags = flags & DPI_BOTH;
   a.k0 = (uint32_t)seed;
@@ -1966,7 +1969,7 @@ int dpi_sample_with_gradients(dpi_problem p, dpi_net net, int n, int M, int K, u
     return dpi_generate_with_gradients(p, net, tx, n, M, K, seed, epoch, point_base, flags, sample_bound, y, moments, ws,
                                        ws_bytes, stream);
   }
-  if (fused_base_ok(p, net) && M % P == 0 && M / P <= 64 && fused_reduce_on() && fused_base_on()) {
+  if (fused_base_ok(p, net) && (M + P - 1) / P <= 64 && fused_reduce_on() && fused_base_on()) {
     WsLayout wl;
     PathArgs a;
     if ((rc = label_args(p, net, tx, n, M, K, seed, epoch, point_base, 0, M, flags, true, moments, ws, ws_bytes, &wl,
@@ -2288,8 +2291,8 @@ int dpi_generate_with_gradients_and_hessians(dpi_problem p, dpi_net net, const f
                                              float* y, void* ws, size_t ws_bytes, void* stream) {
   int rc = check_pair(p, net);
   if (rc) return rc;
-  if (n < 0 || (!y && n) || M < P || (M % P) || M > 1024 * P)
-    return fail(DPI_ERR_ARG, "generate_with_gradients_and_hessians: bad arguments (M multiple of 64, <= 65536)");
+  if (n < 0 || (!y && n) || M < 1 || M > 1024 * P)
+    return fail(DPI_ERR_ARG, "generate_with_gradients_and_hessians: bad arguments (1 <= M <= 65536)");
   if (n == 0) return 0;
   if (p->e.kind != DPI_EQ_GBM)
     return fail(DPI_ERR_UNSUPPORTED, "Hessian labels need a SimpleDiffusionEquationWithHessian (GBMEquationComplexExact)");

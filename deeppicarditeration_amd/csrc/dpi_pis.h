@@ -716,7 +716,8 @@ __global__ void k_pis_tvalue(EqDev e, NetPisDev pn, const float* __restrict__ tx
 // Per-path f, b_p and label contributions for one (point, 64-path block) -> partial slab.
 template <int KIND, bool X3>
 __global__ __launch_bounds__(256) void k_pis_final(EqDev e, NetPisDev pn, const float* __restrict__ tx, int g0,
-                                                   int nbp, int K, int flags, const float* __restrict__ fbv,
+                                                   int nbp, int m_begin, int m_end, int K, int flags,
+                                                   const float* __restrict__ fbv,
                                                    const float* __restrict__ gxv, const float* __restrict__ rows,
                                                    PisRows L, float* __restrict__ partial, float td_dt) {
   __shared__ float part[4][4][64];  // per-wave 16-path column sums: [wave][q][value]
@@ -755,10 +756,15 @@ __global__ __launch_bounds__(256) void k_pis_final(EqDev e, NetPisDev pn, const 
     }
     ap = gv - gxv[i];
   }
+  // a dead row (MC index >= m_end in the last block of a count that is no multiple of 64; the
+  // rollouts and the chain process whole blocks) adds exactly +0: a_p, b_p and c0 by select
+  const bool live = m_begin + P * b + p < m_end;
+  ap = live ? ap : 0.f;
   const float s = row[L.SC + 0], smt = row[L.SC + 3];
   float A, B, sm;
   pis_z_stats<X3>(e, pn, gmm, row, L, pn.T - s, q, A, B, sm);
-  const float bp = INTG ? tmt * (Eq<KIND>::ffv(e, 0.f, 0.f, A, B) - f_b) : 0.f;
+  const float bpl = INTG ? tmt * (Eq<KIND>::ffv(e, 0.f, 0.f, A, B) - f_b) : 0.f;
+  const float bp = live ? bpl : 0.f;
   const float yT = 1.0f / (sqrtf(Kf * tmt) * e.asq), yI = 1.0f / (sqrtf(Kf * smt) * e.asq);
   // this row's contributions: v[2k + mom] for dim d = 16 (k >> 2) + 4 q + (k & 3) (k < 32: nx <= 128),
   // the value column (lane group q = 0) apart.  The noise sums come in 16-B loads: the 4 lanes of a
@@ -783,7 +789,7 @@ __global__ __launch_bounds__(256) void k_pis_final(EqDev e, NetPisDev pn, const 
       v[2 * k + 1] = c * c;
     }
   }
-  float c0 = q == 0 ? ap + bp + (INTG ? (f_b + Eq<KIND>::ffc(e)) * tmt : 0.f) : 0.f, c0s = c0 * c0;
+  float c0 = q == 0 ? ap + bp + (INTG ? (live ? f_b + Eq<KIND>::ffc(e) : 0.f) * tmt : 0.f) : 0.f, c0s = c0 * c0;
   // sum over the wave's 16 rows (lane = 4 row + q) by a halving butterfly on lane bits 5..2: at bit
   // m a lane keeps the half of its values selected by that bit and adds its partner's copy, so lane
   // (row r, q) ends with values 4r .. 4r + 3 summed over the 16 rows of lane group q.  Bits 5 and 4

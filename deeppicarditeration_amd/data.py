@@ -56,6 +56,14 @@ class SplitRangeWarning(RuntimeWarning):
     generator's later calls made, with exact-fp32 MFMA (DPI_GEMM_F32) for that network."""
 
 
+class PartialBlockNote(UserWarning):
+    """A Monte-Carlo sample count M for which more than half of the launched lanes are dead
+    (ceil64(M) > 2 M): the kernels run whole 64-path blocks, so M = 1 costs what M = 64 costs."""
+
+
+_PARTIAL_NOTED = set()  # (class, M) already warned about
+
+
 # include/dpi.h status ring: slot 0 serves the immediate (per-call) check, UNCHECKED_SLOT collects the
 # flags of calls made with range_check off (never read), the others are handed to RangeGroups
 IMMEDIATE_SLOT = 0
@@ -233,12 +241,15 @@ class OnlineDataGenerator:
     """picard/data.py:369-431 (constructor), :211-223 / :1208-1218 (label entry points)."""
 
     do_internal_batching = True
+    # whether n_estimate_* may be any count >= 1 when the constructor's partial_blocks is None
+    partial_blocks_default = False
 
     def __init__(self, equation: Equation, solution: torch.nn.Module, N: int, i: int, *,
                  device: Union[str, torch.device] = "cuda", t_always_uniform=False, n_estimate_terminal=1,
                  n_estimate_integral=1, hessian_approximation=None, sample_bound=None, estimate_terminal="OU_ByGx",
                  estimate_integral="OU_Simple", estimate_delta_t=0.0, n_euler_steps: int = 50, seed: int = 0,
-                 epoch: int = None, max_points_per_call: int = None, label_dtype: torch.dtype = torch.float32):
+                 epoch: int = None, max_points_per_call: int = None, label_dtype: torch.dtype = torch.float32,
+                 partial_blocks: bool = None):
         if not (isinstance(equation, SimpleDiffusionEquation) or isinstance(equation, OUProcessEquation)):
             raise AssertionError("Currently only SimpleDiffusionEquation and OUProcessEquation are supported")  # :426-429
         if equation.nu != 1:
@@ -265,9 +276,25 @@ class OnlineDataGenerator:
             raise ValueError("the HIP label generator runs on a GPU device ('cuda' on ROCm)")
         self.n_estimate_terminal = int(n_estimate_terminal)
         self.n_estimate_integral = int(n_estimate_integral)
+        # Counts that are no multiple of the 64-path block (the reference takes any; its default is 1,
+        # picard/data.py:379-380) are an opt-in here: partial_blocks=True, or a class whose
+        # partial_blocks_default is True (the runner and the reference binding).  The last block's
+        # lanes past M are dead: they run and add +0 (include/dpi.h dpi_label_moments).
+        blk = _lib.DPI_PATH_BLOCK
+        partial = type(self).partial_blocks_default if partial_blocks is None else bool(partial_blocks)
         for m in (self.n_estimate_terminal, self.n_estimate_integral):
-            if m % _lib.DPI_PATH_BLOCK:
-                raise ValueError(f"Monte-Carlo sample counts must be multiples of {_lib.DPI_PATH_BLOCK} (got {m})")
+            if m < 1:
+                raise ValueError(f"Monte-Carlo sample counts must be >= 1 (got {m})")
+            if m % blk and not partial:
+                raise ValueError(f"Monte-Carlo sample counts must be multiples of {blk} (got {m}); "
+                                 "partial_blocks=True accepts any count >= 1")
+            launched = -(-m // blk) * blk
+            if launched > 2 * m and (type(self), m) not in _PARTIAL_NOTED:
+                _PARTIAL_NOTED.add((type(self), m))
+                warnings.warn(f"a Monte-Carlo sample count of {m} runs as {launched} paths per point of which "
+                              f"{launched - m} are discarded: the kernels work in blocks of {blk} paths, so {m} "
+                              f"{'path costs' if m == 1 else 'paths cost'} what {launched} cost",
+                              PartialBlockNote, stacklevel=2)
         self.sample_bound = float("inf") if sample_bound is None else float(sample_bound)
         self.estimate_terminal_type = estimate_terminal
         self.estimate_integral_type = estimate_integral

@@ -41,9 +41,26 @@ def generator_class(base=None, impl=OnlineDataGenerator):
         return impl
     cls = _CLASSES.get((base, impl))
     if cls is None:
-        cls = type(impl.__name__, (impl, base), {"__module__": __name__, "__doc__": impl.__doc__})
+        # the data module's DATA.kwargs reach the constructor as the reference wrote them: any
+        # n_estimate_* >= 1 (a class default, not a keyword the module would have to pass)
+        cls = type(impl.__name__, (impl, base), {"__module__": __name__, "__doc__": impl.__doc__,
+                                                 "partial_blocks_default": True})
         _CLASSES[(base, impl)] = cls
     return cls
+
+
+def _any_count(cls):
+    """`cls`, or (where its partial_blocks_default is not set) a subclass of it that accepts any
+    n_estimate_* >= 1, cached: the binding takes the reference's sample counts with or without a
+    `base`, and adds no keyword to what the data module forwards."""
+    if getattr(cls, "partial_blocks_default", False):
+        return cls
+    sub = _CLASSES.get((None, cls))
+    if sub is None:
+        sub = type(cls.__name__, (cls,), {"__module__": __name__, "__doc__": cls.__doc__,
+                                          "partial_blocks_default": True})
+        _CLASSES[(None, cls)] = sub
+    return sub
 
 
 def _cfg_get(cfg, key, default):
@@ -93,7 +110,7 @@ def hip_online_data_generator(kws, data_cfg=None, base=None, generator_cls=None)
         raise ValueError(f"DATA.NEW_SAMPLING false with DATA.N_BUFFER {n_buffer!r} would generate all "
                          f"{data_size} points in one call, above DATA.POINTS_PER_CALL = {cap}: set DATA.N_BUFFER "
                          f"(batches per call) or NEW_SAMPLING true")
-    cls = generator_class(base, generator_cls or OnlineDataGenerator)
+    cls = _any_count(generator_class(base, generator_cls or OnlineDataGenerator))
     return cls(equation, solution, N, i, device=device, n_euler_steps=int(_cfg_get(data_cfg, "EULER_STEPS", 50)),
                seed=int(_cfg_get(data_cfg, "SEED", 0)), max_points_per_call=cap,
                label_dtype=label_dtype(_cfg_get(data_cfg, "FLOAT", None)), **kw)

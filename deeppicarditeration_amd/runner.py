@@ -171,6 +171,7 @@ class PicardRunner:
         kw = dict(dict(d.kwargs), hessian_approximation=d.HESSIAN_APPROXIMATION, sample_bound=d.SAMPLE_BOUND,
                   estimate_terminal=d.ESTIMATE_TERMINAL, estimate_integral=d.ESTIMATE_INTEGRAL,
                   estimate_delta_t=d.ESTIMATE_DELTA_T, n_euler_steps=d.EULER_STEPS, seed=d.SEED)
+        kw.setdefault("partial_blocks", True)  # any n_estimate_* >= 1, as the reference (its default is 1)
         kw.update(overrides)
         return OnlineDataGenerator(self.equation, solution, self.N, self.i, device=self.device, **kw)
 

@@ -43,6 +43,8 @@ class ShardedLabeler:
 
     def shard(self, M):
         blk = 64
+        if self.world == 1:  # any M >= 1: the last block's lanes past M are dead (include/dpi.h)
+            return 0, M
         if M % (blk * self.world):
             raise ValueError(f"M={M} must be a multiple of 64 x world ({self.world})")
         per = M // self.world

@@ -42,7 +42,7 @@
 extern "C" {
 #endif
 
-#define DPI_ABI_VERSION 7
+#define DPI_ABI_VERSION 8
 
 /* error codes */
 #define DPI_OK 0
@@ -78,7 +78,8 @@ extern "C" {
 /* dpi_label_moments: dpi_label_prepare already ran on this workspace with the same arguments */
 #define DPI_PREPARED 4
 
-/* Monte-Carlo paths per workgroup: m ranges are multiples of this. */
+/* Monte-Carlo paths per workgroup.  An m range starts at a multiple of this and ends at a multiple
+ * of it or at the sample count M (ABI 8: any M >= 1; the last workgroup's lanes past M add +0). */
 #define DPI_PATH_BLOCK 64
 /* paths (m_end - m_begin) one label-moments call takes: 1024 path blocks per point */
 #define DPI_PATHS_PER_CALL_MAX 65536
@@ -199,7 +200,7 @@ int dpi_launch_timer_ms(int slot, float* ms);
 size_t dpi_workspace_bytes(dpi_problem p, dpi_net net, int n, int M);
 
 /* Workspace of dpi_label_prepare and of the DPI_PREPARED dpi_label_moments call it feeds: for a GBM
- * MLP net it adds the staged noise sums ((n, M / 64, 2, 4 ceil(nx / 4), 64) floats), otherwise it
+ * MLP net it adds the staged noise sums ((n, ceil(M / 64), 2, 4 ceil(nx / 4), 64) floats), otherwise it
  * equals dpi_workspace_bytes. */
 size_t dpi_workspace_bytes_prepared(dpi_problem p, dpi_net net, int n, int M);
 
@@ -221,8 +222,12 @@ int dpi_sample_points_t(dpi_problem p, int n, uint64_t seed, uint32_t epoch, uin
 int dpi_point_baseline(dpi_problem p, dpi_net net, const float* tx, int n, void* ws, size_t ws_bytes,
                        void* stream);
 
-/* Label moments over MC indices m in [m_begin, m_end) of M (both multiples of DPI_PATH_BLOCK)
- * with K Euler–Maruyama steps per path.  moments (n, 2, 1+nx) fp32: [0] = sum of per-path
+/* Label moments over MC indices m in [m_begin, m_end) of M with K Euler–Maruyama steps per path.
+ * m_begin is a multiple of DPI_PATH_BLOCK; m_end is a multiple of it or equals M (ABI 8: M >= 1 is
+ * otherwise free).  A range that ends at an M inside a block still launches ceil((m_end - m_begin) /
+ * 64) workgroups per point; the lanes of the last one with m >= m_end roll out like any other and
+ * contribute exactly +0 to every sum, so the block tree, dpi_moments_reduce and the 1 / M of the
+ * finalize calls are those of whole blocks (M = 1 costs what M = 64 costs).  moments (n, 2, 1+nx) fp32: [0] = sum of per-path
  * contributions, [1] = sum of squares.  Summation order is fixed (pairwise over 64-path
  * blocks), so results are bit-reproducible; ranges aligned to power-of-two block counts
  * combine with dpi_moments_reduce bit-identically to a single call.  Requires
@@ -273,7 +278,7 @@ int dpi_generate_with_gradients(dpi_problem p, dpi_net net, const float* tx, int
 /* sample_with_gradients(n): the n points of dpi_sample_points_t (eps, t_factors, point_base as
  * there) into tx (n, 1+nx), then dpi_generate_with_gradients on them — tx, y and moments bitwise
  * those of the two separate calls, and the workspace's baseline that of dpi_point_baseline.
- * First-order Cha / OU labels of MLP and zero networks (no TD, M <= 4096) run as ONE launch: n
+ * First-order Cha / OU labels of MLP and zero networks (no TD, ceil(M / 64) <= 64) run as ONE launch: n
  * baseline workgroups ahead of the path workgroups, which draw their point themselves and wait for
  * its baseline (an in-launch hand-off) before the network evaluation; the label reduce runs in the
  * path launch (DPI_FUSED_BASE=0: two launches, the sampling inside the baseline launch).  GBM: two
@@ -295,7 +300,7 @@ int dpi_sample_points_baseline(dpi_problem p, dpi_net net, int n, uint64_t seed,
  * y: (n, 1 + nx + nx*nx) = [u, grad u, Hessian (row-major)], f evaluated with the full Hessian
  * diagonal whatever the problem's SDGD setting (the reference calls get_f without the SDGD
  * context there).  GBMEquationComplexExact problems (the reference asserts
- * SimpleDiffusionEquationWithHessian), MLP (width <= 64) or zero networks; M % 64 == 0, M <= 65536.
+ * SimpleDiffusionEquationWithHessian), MLP (width <= 64) or zero networks; 1 <= M <= 65536 (ABI 8).
  * Noise: the first-order streams plus N1 = tag DPI_TAG_HTERM, N2 = tag DPI_TAG_HINT (k = 0).
  * ws >= dpi_workspace_bytes_hessians(p, net, n, M). */
 size_t dpi_workspace_bytes_hessians(dpi_problem p, dpi_net net, int n, int M);

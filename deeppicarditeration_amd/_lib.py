@@ -24,6 +24,7 @@ DPI_GEMM_F32, DPI_GEMM_F16X3, DPI_GEMM_AUTO = 0, 1, 2
 DPI_STATUS_NONFINITE = 1
 DPI_STATUS_HANDOFF = 2
 DPI_STATUS_SLOTS = 64
+DPI_FAMILY_SPECIALISED, DPI_FAMILY_GENERAL = 0, 1  # dpi_pair_family
 
 c_int, c_double, c_float, c_size_t, c_void_p, c_uint32, c_uint64 = (
     ctypes.c_int, ctypes.c_double, ctypes.c_float, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64)
@@ -44,6 +45,8 @@ SIGNATURES = {
     "dpi_net_create_mlp": (c_int, [c_int, c_int, P(c_int), c_int, P(c_float), c_size_t, P(c_void_p)]),
     "dpi_net_create_pisgrad": (c_int, [c_int, c_int, P(c_int), c_double, P(c_float), c_size_t, P(c_void_p)]),
     "dpi_net_destroy": (c_int, [c_void_p]),
+    "dpi_pair_family": (c_int, [c_void_p, c_void_p, c_int, P(c_int)]),
+    "dpi_general_slots": (c_int, [c_void_p, P(c_int)]),
     "dpi_set_gemm_precision": (c_int, [c_int]),
     "dpi_net_set_precision": (c_int, [c_void_p, c_int]),
     "dpi_net_status": (c_int, [c_void_p, c_int, c_void_p, P(c_int)]),

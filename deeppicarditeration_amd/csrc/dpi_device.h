@@ -1805,6 +1805,10 @@ __global__ __launch_bounds__(NTHB) void k_baseline_gbm(EqDev e, NetDev net, cons
   if (tid == 0) fb[i] = Cb;
 }
 
+}  // namespace dpi
+#include "dpi_general.h"
+namespace dpi {
+
 struct PathArgs {
   const float* tx;
   const float* gx;
@@ -2236,14 +2240,22 @@ constexpr int k_paths_wgs() {
 // fb.nbase blocks are the points' base blocks — a kernel of its own, so the plain k_paths keeps its
 // register allocation (the hand-off's arguments live across the whole kernel).
 // NXW: the state-dimension cap of the instance (NXP_MAX; NXW_MAX for the wide first-order instances)
-template <int KIND, int H, int L, bool ZERO, bool SPLIT, bool HESS, bool TD, int ACT, bool FBT, int NXW = NXP_MAX>
-__device__ __forceinline__ void paths_body(const EqDev& e, const NetDev& net, const PathArgs& a, const FusedBase& fb) {
+// NET = NetGen: the general MLP family (k_paths_gen; H is its width cap HCAP, L unused — the net's
+// layer count is read at run time): phase 2 is mlp_tile_gen, gbid is the block index within the call
+// (the launch's first block + blockIdx.x) and stash the workgroup's stash slot.
+template <int KIND, int H, int L, bool ZERO, bool SPLIT, bool HESS, bool TD, int ACT, bool FBT, int NXW = NXP_MAX,
+          class NET = NetDev>
+__device__ __forceinline__ void paths_body(const EqDev& e, const NET& net, const PathArgs& a, const FusedBase& fb,
+                                           unsigned gbid = 0u, floatx4* stash = nullptr) {
+  constexpr bool GEN = std::is_same_v<NET, NetGen>;
+  static_assert(!GEN || (KIND != DPI_EQ_GBM && !ZERO && !SPLIT && !HESS && !TD && !FBT && NXW == NXP_MAX),
+                "the general family: first-order Cha / OU labels, exact fp32, nx <= 128");
   static_assert(!HESS || KIND == DPI_EQ_GBM, "Hessian labels: GBM (SimpleDiffusionEquationWithHessian) only");
   static_assert(!(HESS && TD), "the Hessian-label estimators have no TD variant (data.py:1220-1223)");
   static_assert(NXW == NXP_MAX || (!HESS && !TD && !FBT && NXW % 128 == 0 && NXW <= NXW_MAX),
                 "wide instances: first-order labels, no TD, no fused baseline");
   static_assert(!(KIND == DPI_EQ_GBM && NXW > NXP_MAX) || L <= 3, "wide GBM instances: the hidden weights of L <= 3");
-  using SH = std::conditional_t<KIND == DPI_EQ_GBM, LdsGbm<H, NXW>, LdsT<NXW>>;
+  using SH = std::conditional_t<GEN, LdsGen<H>, std::conditional_t<KIND == DPI_EQ_GBM, LdsGbm<H, NXW>, LdsT<NXW>>>;
   constexpr int NBW = NXW / 16;  // dim-blocks of 4 per wave (4 waves)
   __shared__ SH sh;
   constexpr bool GBM = KIND == DPI_EQ_GBM;
@@ -2261,7 +2273,7 @@ __device__ __forceinline__ void paths_body(const EqDev& e, const NetDev& net, co
       return;
     }
   }
-  const unsigned bid = blockIdx.x - (FB ? (unsigned)fb.nbase : 0u);
+  const unsigned bid = GEN ? gbid : blockIdx.x - (FB ? (unsigned)fb.nbase : 0u);
   const int i = bid / a.nbp;
   const int blk = bid - i * a.nbp;
   // independent Philox chains per wave in the noise loops (2 vs 1: 2 % on the one- and two-wave-per-SIMD
@@ -2331,8 +2343,13 @@ __device__ __forceinline__ void paths_body(const EqDev& e, const NetDev& net, co
       sh.vec[2 * H + h] = net.wout[h];
       sh.vec[3 * H + h] = net.c1[h];
     }
-    for (int l = 1; l < L; ++l)
-      for (int h = tid; h < H; h += NTH) sh.bh[l * H + h] = net.b[l][h];
+    if constexpr (GEN) {
+      for (int l = 1; l < net.L; ++l)
+        for (int h = tid; h < H; h += NTH) sh.bh[l * H + h] = net.b[l][h];
+    } else {
+      for (int l = 1; l < L; ++l)
+        for (int h = tid; h < H; h += NTH) sh.bh[l * H + h] = net.b[l][h];
+    }
   }
   if constexpr (GBM) {
     if (!ZERO) {  // all weights resident for the tangent sweep (wide instances: W1x from L2)
@@ -2484,7 +2501,9 @@ __device__ __forceinline__ void paths_body(const EqDev& e, const NetDev& net, co
     if constexpr (!GBM) {
       float u = 0.f, gs = 0.f, gA = 0.f, gB = 0.f;
       if (!ZERO && INTG) {
-        if constexpr (SPLIT)
+        if constexpr (GEN)
+          mlp_tile_gen<KIND, H, ACT>(e, net, sh, stash, u, gs, gA, gB);
+        else if constexpr (SPLIT)
           mlp_tile_split<KIND, H, L, ACT>(e, net, sh, u, gs, gA, gB);
         else
           mlp_tile<KIND, H, L, ACT>(e, net, sh, nxp / 16, u, gs, gA, gB, nullptr, 0, P);
@@ -2544,6 +2563,8 @@ __device__ __forceinline__ void paths_body(const EqDev& e, const NetDev& net, co
   bool tlast = false;
   if constexpr (TD) {
     tlast = false;  // the terminal MLP needs the noise tile before the integral rollout
+  } else if constexpr (GEN) {
+    tlast = true;  // the terminal sums are not live across the MLP (its two layers of registers)
   } else if constexpr (SPLIT && !GBM) {
     tlast = true;  // measured faster, and the terminal sums are not live across the MLP (no spills)
   } else if constexpr (!GBM) {
@@ -2573,7 +2594,7 @@ __device__ __forceinline__ void paths_body(const EqDev& e, const NetDev& net, co
     if constexpr (!ZERO) {
       if constexpr (GBM) {
         u = mlp_value_res<H, L, ACT>(net, sh, nxp / 16);
-      } else {
+      } else if constexpr (!GEN) {
         float gs, gA, gB;
         if constexpr (SPLIT)
           mlp_tile_split<KIND, H, L, ACT>(e, net, sh, u, gs, gA, gB);
@@ -2771,6 +2792,19 @@ template <int KIND, int H, int L, bool ZERO, bool SPLIT, int ACT = DPI_ACT_ELU>
 __global__ __launch_bounds__(256, (k_paths_wgs<KIND, H, L, SPLIT, false>())) void k_paths_fb(EqDev e, NetDev net,
                                                                                             PathArgs a, FusedBase fb) {
   paths_body<KIND, H, L, ZERO, SPLIT, false, false, ACT, true>(e, net, a, fb);
+}
+// The general MLP family's path launch (dpi_general.h): the (point, 64-path block) pairs
+// [block0, block0 + gridDim.x) of the call, gridDim.x <= gen_slots(HCAP); workgroup blockIdx.x owns
+// stash slot blockIdx.x.  The host runs a call as consecutive launches of such ranges on the call's
+// stream (dpi_dispatch.h dispatch_gen), so a slot has one user at a time; a block's arithmetic does
+// not depend on the range it runs in.  (A grid-stride loop over the ranges inside one launch kept
+// every kernel argument live around the whole body: 356 spilled VGPRs at HCAP = 128.)
+template <int KIND, int HCAP, int ACT>
+__global__ __launch_bounds__(256, (gen_wgs(HCAP))) void k_paths_gen(EqDev e, NetGen net, PathArgs a, floatx4* stash,
+                                                                  unsigned block0) {
+  floatx4* const slot = stash + (size_t)blockIdx.x * (gen_slot_floats(net.L, net.ht) / 4);
+  paths_body<KIND, HCAP, GEN_LMAX, false, false, false, false, ACT, false, NXP_MAX, NetGen>(e, net, a, FusedBase{},
+                                                                                             block0 + blockIdx.x, slot);
 }
 
 }  // namespace dpi

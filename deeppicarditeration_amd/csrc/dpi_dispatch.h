@@ -18,6 +18,12 @@ struct dpi_problem_s {
 struct dpi_net_s {
   NetDev d;        // d.kind: 0 zero, 1 mlp, 2 PISGradNet
   NetPisDev pis;
+  // MLP nets: which device images the upload built.  spec: d's (the specialised k_paths instances:
+  // L <= 4, widths <= 128); gen: g's (the general family, dpi_general.h), built for every net that has
+  // no specialised first-order Cha / OU instance.  A net may hold both — (32, 3) is specialised for
+  // GBM only, and the upload does not know the equation.
+  NetGen g{};
+  bool spec = true, gen = false;
   void* blob = nullptr;
   int n_in = 0;
   int precision = -1;     // DPI_GEMM_* for this net (dpi_net_set_precision); -1: the process-wide mode
@@ -48,6 +54,8 @@ struct Launch {
   // dpi_launch_timer_arm: the path launch's own start / stop timestamps (hipExtLaunchKernel records
   // them on the dispatch packet itself — no marker packets between the launches); null: untimed
   hipEvent_t t0 = nullptr, t1 = nullptr;
+  bool gen = false;         // the pair runs the general MLP family (dpi_kernels.hip pair_route)
+  floatx4* stash = nullptr;  // its stash region of the workspace (path launches)
 };
 // The path launches (k_paths, k_paths_fb) of a Launch, with its timer events when armed.
 #define DPI_PATH_LAUNCH(KERN, q, ...) \
@@ -116,8 +124,58 @@ void do_launch(const dpi_problem_s* p, const dpi_net_s* net, const Launch& q) {
     launch_paths<KIND, H, L, Z, ACT, false, false, NXW>(p->e, net, q);
 }
 
-template <int KIND, bool TDV = false, int ACT = DPI_ACT_ELU, bool FBV = false, int NXW = NXP_MAX>
+// The (H, L) pairs with a specialised k_paths instance: H the padded width class, L the hidden layers.
+// GBM keeps every weight LDS-resident: H <= 64.
+#define DPI_SHAPES_GBM(X) X(64, 3) X(64, 2) X(32, 2) X(32, 3) X(16, 1) X(16, 2) X(16, 3)
+#define DPI_SHAPES_FO(X) X(128, 4) X(128, 3) X(128, 2) X(64, 3) X(64, 2) X(32, 2) X(16, 1) X(16, 2) X(16, 3)
+constexpr bool spec_shape(int kind, int H, int L) {
+#define DPI_SHAPE(HH, LL) \
+  if (H == HH && L == LL) return true;
+  if (kind == DPI_EQ_GBM) {
+    DPI_SHAPES_GBM(DPI_SHAPE)
+  } else {
+    DPI_SHAPES_FO(DPI_SHAPE)
+  }
+#undef DPI_SHAPE
+  return false;
+}
+
+// The general MLP family's units (GENV rows of DPI_UNITS): k_paths_gen at both width caps, and — in
+// the ELU units, like k_baseline — the activation-generic k_baseline_gen.
+template <int KIND, int ACT>
+bool dispatch_gen(const dpi_problem_s* p, const dpi_net_s* net, const Launch& q) {
+  const NetGen& g = net->g;
+  if (q.baseline) {
+    if constexpr (ACT == DPI_ACT_ELU) {
+      hipLaunchKernelGGL((k_baseline_gen<KIND>), dim3(q.n), dim3(NTB), 0, q.st, p->e, g, q.tx, q.n, q.gx, q.fb, q.bx,
+                         q.smp, q.tickets);
+      return true;
+    }
+    return false;
+  }
+  if (q.hess || q.td || q.fbase || !q.stash) return false;
+  // block ranges of at most one workgroup per stash slot, in stream order (an armed launch timer
+  // brackets the first range)
+  const unsigned nblocks = (unsigned)q.nblocks, slots = (unsigned)gen_slots(g.H);
+  for (unsigned b0 = 0; b0 < nblocks; b0 += slots) {
+    const unsigned grid = std::min(nblocks - b0, slots);
+    hipEvent_t t0 = b0 ? nullptr : q.t0, t1 = b0 ? nullptr : q.t1;
+    if (g.H == 128)
+      hipExtLaunchKernelGGL((k_paths_gen<KIND, 128, ACT>), dim3(grid), dim3(NTH), 0, q.st, t0, t1, 0, p->e, g, *q.a,
+                            q.stash, b0);
+    else
+      hipExtLaunchKernelGGL((k_paths_gen<KIND, 256, ACT>), dim3(grid), dim3(NTH), 0, q.st, t0, t1, 0, p->e, g, *q.a,
+                            q.stash, b0);
+  }
+  return true;
+}
+
+template <int KIND, bool TDV = false, int ACT = DPI_ACT_ELU, bool FBV = false, int NXW = NXP_MAX, bool GENV = false>
 bool dpi_dispatch(const dpi_problem_s* p, const dpi_net_s* net, const Launch& q) {
+  if constexpr (GENV) {
+    static_assert(KIND != DPI_EQ_GBM && !TDV && !FBV && NXW == NXP_MAX, "the general family: first-order Cha / OU");
+    return dispatch_gen<KIND, ACT>(p, net, q);
+  } else {
   if constexpr (NXW > NXP_MAX) {
     if (q.baseline || q.hess || q.fbase) return false;
   }
@@ -143,55 +201,46 @@ bool dpi_dispatch(const dpi_problem_s* p, const dpi_net_s* net, const Launch& q)
     do_launch<KIND, HH, LL, false, TDV, ACT, FBV, NXW>(p, net, q); \
     return true;                               \
   }
-    DPI_SHAPE(64, 3)
-    DPI_SHAPE(64, 2)
-    DPI_SHAPE(32, 2)
-    DPI_SHAPE(32, 3)
-    DPI_SHAPE(16, 1)
-    DPI_SHAPE(16, 2)
-    DPI_SHAPE(16, 3)
+    DPI_SHAPES_GBM(DPI_SHAPE)
     return false;
   } else {
-    DPI_SHAPE(128, 4)
-    DPI_SHAPE(128, 3)
-    DPI_SHAPE(128, 2)
-    DPI_SHAPE(64, 3)
-    DPI_SHAPE(64, 2)
-    DPI_SHAPE(32, 2)
-    DPI_SHAPE(16, 1)
-    DPI_SHAPE(16, 2)
-    DPI_SHAPE(16, 3)
+    DPI_SHAPES_FO(DPI_SHAPE)
 #undef DPI_SHAPE
     return false;
+  }
   }
 }
 
 // ---- the unit table: one row per dpi_paths_*.hip translation unit, keyed by dpi_dispatch's template
-// arguments (KIND, TDV, ACT, FBV, NXW).  Each unit file holds the explicit instantiation of its row
+// arguments (KIND, TDV, ACT, FBV, NXW, GENV).  Each unit file holds the explicit instantiation of its row
 // (DPI_UNIT_DEFINE) and nothing else; every other unit sees the row as an extern template, so a row
 // without a unit fails at link time.  dpi_kernels.hip dispatch_any derives the key of a launch and
 // looks it up here.
 #define DPI_UNITS(X)                                                \
-  X(cha, DPI_EQ_CHA, false, DPI_ACT_ELU, false, NXP_MAX)            \
-  X(ou, DPI_EQ_OU, false, DPI_ACT_ELU, false, NXP_MAX)              \
-  X(gbm, DPI_EQ_GBM, false, DPI_ACT_ELU, false, NXP_MAX)            \
-  X(td_cha, DPI_EQ_CHA, true, DPI_ACT_ELU, false, NXP_MAX)          \
-  X(td_ou, DPI_EQ_OU, true, DPI_ACT_ELU, false, NXP_MAX)            \
-  X(td_gbm, DPI_EQ_GBM, true, DPI_ACT_ELU, false, NXP_MAX)          \
-  X(cha_tanh, DPI_EQ_CHA, false, DPI_ACT_TANH, false, NXP_MAX)      \
-  X(ou_tanh, DPI_EQ_OU, false, DPI_ACT_TANH, false, NXP_MAX)        \
-  X(gbm_tanh, DPI_EQ_GBM, false, DPI_ACT_TANH, false, NXP_MAX)      \
-  X(td_cha_tanh, DPI_EQ_CHA, true, DPI_ACT_TANH, false, NXP_MAX)    \
-  X(td_ou_tanh, DPI_EQ_OU, true, DPI_ACT_TANH, false, NXP_MAX)      \
-  X(td_gbm_tanh, DPI_EQ_GBM, true, DPI_ACT_TANH, false, NXP_MAX)    \
-  X(fb_cha, DPI_EQ_CHA, false, DPI_ACT_ELU, true, NXP_MAX)          \
-  X(fb_ou, DPI_EQ_OU, false, DPI_ACT_ELU, true, NXP_MAX)            \
-  X(wide_cha, DPI_EQ_CHA, false, DPI_ACT_ELU, false, NXW_MAX)       \
-  X(wide_ou, DPI_EQ_OU, false, DPI_ACT_ELU, false, NXW_MAX)         \
-  X(wide_gbm, DPI_EQ_GBM, false, DPI_ACT_ELU, false, NXW_MAX)       \
-  X(wide_cha_tanh, DPI_EQ_CHA, false, DPI_ACT_TANH, false, NXW_MAX) \
-  X(wide_ou_tanh, DPI_EQ_OU, false, DPI_ACT_TANH, false, NXW_MAX)   \
-  X(wide_gbm_tanh, DPI_EQ_GBM, false, DPI_ACT_TANH, false, NXW_MAX)
+  X(cha, DPI_EQ_CHA, false, DPI_ACT_ELU, false, NXP_MAX, false)            \
+  X(ou, DPI_EQ_OU, false, DPI_ACT_ELU, false, NXP_MAX, false)              \
+  X(gbm, DPI_EQ_GBM, false, DPI_ACT_ELU, false, NXP_MAX, false)            \
+  X(td_cha, DPI_EQ_CHA, true, DPI_ACT_ELU, false, NXP_MAX, false)          \
+  X(td_ou, DPI_EQ_OU, true, DPI_ACT_ELU, false, NXP_MAX, false)            \
+  X(td_gbm, DPI_EQ_GBM, true, DPI_ACT_ELU, false, NXP_MAX, false)          \
+  X(cha_tanh, DPI_EQ_CHA, false, DPI_ACT_TANH, false, NXP_MAX, false)      \
+  X(ou_tanh, DPI_EQ_OU, false, DPI_ACT_TANH, false, NXP_MAX, false)        \
+  X(gbm_tanh, DPI_EQ_GBM, false, DPI_ACT_TANH, false, NXP_MAX, false)      \
+  X(td_cha_tanh, DPI_EQ_CHA, true, DPI_ACT_TANH, false, NXP_MAX, false)    \
+  X(td_ou_tanh, DPI_EQ_OU, true, DPI_ACT_TANH, false, NXP_MAX, false)      \
+  X(td_gbm_tanh, DPI_EQ_GBM, true, DPI_ACT_TANH, false, NXP_MAX, false)    \
+  X(fb_cha, DPI_EQ_CHA, false, DPI_ACT_ELU, true, NXP_MAX, false)          \
+  X(fb_ou, DPI_EQ_OU, false, DPI_ACT_ELU, true, NXP_MAX, false)            \
+  X(wide_cha, DPI_EQ_CHA, false, DPI_ACT_ELU, false, NXW_MAX, false)       \
+  X(wide_ou, DPI_EQ_OU, false, DPI_ACT_ELU, false, NXW_MAX, false)         \
+  X(wide_gbm, DPI_EQ_GBM, false, DPI_ACT_ELU, false, NXW_MAX, false)       \
+  X(wide_cha_tanh, DPI_EQ_CHA, false, DPI_ACT_TANH, false, NXW_MAX, false) \
+  X(wide_ou_tanh, DPI_EQ_OU, false, DPI_ACT_TANH, false, NXW_MAX, false)   \
+  X(wide_gbm_tanh, DPI_EQ_GBM, false, DPI_ACT_TANH, false, NXW_MAX, false) \
+  X(gen_cha, DPI_EQ_CHA, false, DPI_ACT_ELU, false, NXP_MAX, true) \
+  X(gen_ou, DPI_EQ_OU, false, DPI_ACT_ELU, false, NXP_MAX, true) \
+  X(gen_cha_tanh, DPI_EQ_CHA, false, DPI_ACT_TANH, false, NXP_MAX, true) \
+  X(gen_ou_tanh, DPI_EQ_OU, false, DPI_ACT_TANH, false, NXP_MAX, true)
 
 struct Unit {
   int kind;
@@ -199,9 +248,10 @@ struct Unit {
   int act;
   bool fb;
   int nxw;
+  bool gen;
   bool (*dispatch)(const dpi_problem_s*, const dpi_net_s*, const Launch&);
-  constexpr bool is(int k, bool t, int a, bool f, int w) const {
-    return kind == k && td == t && act == a && fb == f && nxw == w;
+  constexpr bool is(int k, bool t, int a, bool f, int w, bool g = false) const {
+    return kind == k && td == t && act == a && fb == f && nxw == w && gen == g;
   }
 };
 #define DPI_UNIT_EXTERN(NAME, ...) \
@@ -218,13 +268,13 @@ constexpr Unit UNITS[N_UNITS] = {DPI_UNITS(DPI_UNIT_ROW)};
 constexpr bool units_distinct() {
   for (int i = 0; i < N_UNITS; ++i)
     for (int j = 0; j < i; ++j)
-      if (UNITS[i].is(UNITS[j].kind, UNITS[j].td, UNITS[j].act, UNITS[j].fb, UNITS[j].nxw)) return false;
+      if (UNITS[i].is(UNITS[j].kind, UNITS[j].td, UNITS[j].act, UNITS[j].fb, UNITS[j].nxw, UNITS[j].gen)) return false;
   return true;
 }
-static_assert(units_distinct(), "two rows of DPI_UNITS share a (KIND, TDV, ACT, FBV, NXW) key");
+static_assert(units_distinct(), "two rows of DPI_UNITS share a (KIND, TDV, ACT, FBV, NXW, GENV) key");
 
 // The whole of dpi_paths_<NAME>.hip: the row's template arguments are written in DPI_UNITS only.
 #define DPI_UNIT_DEFINE(NAME)                                                                                   \
   template bool dpi_dispatch<UNITS[UNIT_##NAME].kind, UNITS[UNIT_##NAME].td, UNITS[UNIT_##NAME].act,            \
-                             UNITS[UNIT_##NAME].fb, UNITS[UNIT_##NAME].nxw>(const dpi_problem_s*, const dpi_net_s*, \
-                                                                            const Launch&);
+                             UNITS[UNIT_##NAME].fb, UNITS[UNIT_##NAME].nxw, UNITS[UNIT_##NAME].gen>(               \
+      const dpi_problem_s*, const dpi_net_s*, const Launch&);

@@ -728,26 +728,31 @@ int dpi_net_create_mlp(int n_in, int n_hidden, const int* widths, int act, const
                        dpi_net* out) {
   if (n_in - 1 > NXW_MAX)
     return fail(DPI_ERR_UNSUPPORTED, "mlp: nx = n_in - 1 exceeds the compiled maximum state dimension 256 (NXW_MAX)");
-  if (!out || !widths || !params || n_in < 2 || n_hidden < 1 || n_hidden > 4)
-    return fail(DPI_ERR_ARG, "mlp: bad arguments");
+  if (!out || !widths || !params || n_in < 2 || n_hidden < 1) return fail(DPI_ERR_ARG, "mlp: bad arguments");
+  if (n_hidden > GEN_LMAX) return fail(DPI_ERR_UNSUPPORTED, "mlp: at most 8 hidden layers (GEN_LMAX)");
   if (act != DPI_ACT_ELU && act != DPI_ACT_TANH)
     return fail(DPI_ERR_UNSUPPORTED, "mlp: activations must be DPI_ACT_ELU or DPI_ACT_TANH");
-  // Any hidden widths up to 128: the layers are zero-padded to the smallest compiled width H in
-  // {16, 32, 64, 128} that holds the widest one.  A padded unit has zero weights and bias in and
-  // zero weights out, so its activation (ELU(0) = tanh(0) = 0) and every gradient through it add
-  // exact zeros: the labels are those of the unpadded network.
+  // Any hidden widths up to 256, up to 8 layers.  Up to 4 layers of widths <= 128 the net gets the
+  // specialised image: the layers zero-padded to the smallest compiled width H in {16, 32, 64, 128}
+  // that holds the widest one.  A padded unit has zero weights and bias in and zero weights out, so
+  // its activation (ELU(0) = tanh(0) = 0) and every gradient through it add exact zeros: the labels
+  // are those of the unpadded network.  A net without a specialised first-order Cha / OU instance of
+  // its (H, L) also (or only) gets the general family's image, padded the same way to 128 or 256.
   int wmax = 0;
   size_t expect = 0;
   for (int l = 0; l < n_hidden; ++l) {
-    if (widths[l] < 1 || widths[l] > HMAX) return fail(DPI_ERR_UNSUPPORTED, "mlp: hidden widths must be in [1, 128]");
+    if (widths[l] < 1 || widths[l] > GEN_HMAX)
+      return fail(DPI_ERR_UNSUPPORTED, "mlp: hidden widths must be in [1, 256] (GEN_HMAX)");
     wmax = std::max(wmax, widths[l]);
     expect += (size_t)widths[l] * ((l ? widths[l - 1] : n_in) + 1);
   }
   expect += (size_t)widths[n_hidden - 1] + 1;
   if (n_params != expect) return fail(DPI_ERR_ARG, "mlp: parameter count mismatch");
   const float* const given = params;  // the finiteness scan (range guard) reads the caller's values
-  const int H = wmax <= 16 ? 16 : wmax <= 32 ? 32 : wmax <= 64 ? 64 : 128;
+  const int H = wmax <= 16 ? 16 : wmax <= 32 ? 32 : wmax <= 64 ? 64 : wmax <= 128 ? 128 : 256;
   const int nx = n_in - 1, L = n_hidden;
+  const bool spec = L <= 4 && wmax <= HMAX;                 // the specialised image (NetDev)
+  const bool gen = !spec || !spec_shape(DPI_EQ_CHA, H, L);  // the general image (NetGen); Cha and OU share a list
   // nx padded to 16 (the fp32 weight images) and to 32 (the split ones).  The split layer-1 rows are
   // LDS chunks of at most 128 words whose 16-B granules are XOR-swizzled by row (split_swz): a closed
   // permutation only for 8, 16 or 32 granules per row, so a chunk of 96 words (nx in 65..96, or
@@ -786,57 +791,96 @@ int dpi_net_create_mlp(int n_in, int n_hidden, const int* widths, int act, const
     blob.resize(off + ((cnt + 3) & ~size_t(3)), 0.f);
     return off;
   };
+  // ---- the general image: the equal-width-H parameters (above) re-laid with row stride HC
+  const int HC = H <= 128 ? 128 : 256, nxg = (nx + 15) & ~15, nxg32 = (nx + 31) & ~31;
+  size_t gW1x = 0, gw1t = 0, gb1 = 0, gc1 = 0, gW1xT = 0, gW[GEN_LMAX] = {0}, gWT[GEN_LMAX] = {0}, gb[GEN_LMAX] = {0},
+         gwout = 0;
+  float gbout = 0.f;
+  if (gen) {
+    const float* q = params;  // (H, n_in) | (H) | [(H, H) | (H)] x (L - 1) | (H) | 1
+    gW1x = take((size_t)HC * nxg), gw1t = take(HC), gb1 = take(HC), gc1 = take(HC), gW1xT = take((size_t)nxg32 * HC);
+    for (int h = 0; h < H; ++h) {
+      double cs = 0;
+      for (int d = 0; d < nx; ++d) {
+        const float w = q[(size_t)h * n_in + 1 + d];
+        blob[gW1x + (size_t)h * nxg + d] = w;
+        blob[gW1xT + (size_t)d * HC + h] = w;
+        cs += w;
+      }
+      blob[gw1t + h] = q[(size_t)h * n_in];
+      blob[gb1 + h] = q[(size_t)H * n_in + h];
+      blob[gc1 + h] = (float)cs;
+    }
+    q += (size_t)H * n_in + H;
+    for (int l = 1; l < L; ++l) {
+      gW[l] = take((size_t)HC * HC), gWT[l] = take((size_t)HC * HC), gb[l] = take(HC);
+      for (int r = 0; r < H; ++r)
+        for (int c = 0; c < H; ++c) {
+          blob[gW[l] + (size_t)r * HC + c] = q[(size_t)r * H + c];
+          blob[gWT[l] + (size_t)c * HC + r] = q[(size_t)r * H + c];
+        }
+      q += (size_t)H * H;
+      for (int h = 0; h < H; ++h) blob[gb[l] + h] = q[h];
+      q += H;
+    }
+    gwout = take(HC);
+    for (int h = 0; h < H; ++h) blob[gwout + h] = q[h];
+    gbout = q[H];
+  }
   const float* W0 = params;
   const float* b0 = W0 + (size_t)H * n_in;
-  const size_t oW1x = take((size_t)H * nxp), ow1t = take(H), ob1 = take(H), oc1 = take(H), oW1xT = take((size_t)nxp * H);
-  for (int h = 0; h < H; ++h) {
-    double cs = 0;
-    for (int d = 0; d < nx; ++d) {
-      const float w = W0[(size_t)h * n_in + 1 + d];
-      blob[oW1x + (size_t)h * nxp + d] = w;
-      blob[oW1xT + (size_t)d * H + h] = w;
-      cs += w;
-    }
-    blob[ow1t + h] = W0[(size_t)h * n_in];
-    blob[ob1 + h] = b0[h];
-    blob[oc1 + h] = (float)cs;
-  }
-  const float* cur = b0 + H;
-  size_t oW[4] = {0}, oWT[4] = {0}, ob[4] = {0};
-  for (int l = 1; l < L; ++l) {
-    oW[l] = take((size_t)H * H);
-    oWT[l] = take((size_t)H * H);
-    ob[l] = take(H);
-    for (int r = 0; r < H; ++r)
-      for (int c = 0; c < H; ++c) {
-        blob[oW[l] + (size_t)r * H + c] = cur[(size_t)r * H + c];
-        blob[oWT[l] + (size_t)c * H + r] = cur[(size_t)r * H + c];
-      }
-    cur += (size_t)H * H;
-    for (int h = 0; h < H; ++h) blob[ob[l] + h] = cur[h];
-    cur += H;
-  }
-  const size_t owout = take(H);
-  for (int h = 0; h < H; ++h) blob[owout + h] = cur[h];
-  const float bout = cur[H];
-  // fp16-split copies for the split MFMA path (H % 32 == 0)
+  size_t oW1x = 0, ow1t = 0, ob1 = 0, oc1 = 0, oW1xT = 0, oW[4] = {0}, oWT[4] = {0}, ob[4] = {0}, owout = 0;
+  float bout = 0.f;
   size_t oW1xS = 0, oW1xTS = 0, oWS[4] = {0}, oWTS[4] = {0}, oWU[4] = {0};
   float wus[4] = {1.f, 1.f, 1.f, 1.f};
   int ea[4] = {0, 0, 0, 0}, eb[4] = {0, 0, 0, 0};  // mlp_hdiag_split's operand exponents
-  if (H % 32 == 0) {
-    auto Wx = [&](int h, int d) { return d < nx ? W0[(size_t)h * n_in + 1 + d] : 0.f; };
-    oW1xS = pack_split(blob, H, nxp32, Wx);
-    oW1xTS = pack_split(blob, nxp32, H, [&](int d, int h) { return Wx(h, d); });
-    for (int l = 1; l < L; ++l) {
-      const float* Wl = blob.data() + oW[l];
-      std::vector<float> Wc(Wl, Wl + (size_t)H * H);
-      oWS[l] = pack_split(blob, H, H, [&](int r, int c) { return Wc[(size_t)r * H + c]; });
-      oWTS[l] = pack_split(blob, H, H, [&](int r, int c) { return Wc[(size_t)c * H + r]; });
-      oWU[l] = pack_split_x3(blob, H, H, [&](int r, int c) { return Wc[(size_t)r * H + c]; }, &wus[l]);
+  if (spec) {
+    oW1x = take((size_t)H * nxp), ow1t = take(H), ob1 = take(H), oc1 = take(H), oW1xT = take((size_t)nxp * H);
+    for (int h = 0; h < H; ++h) {
+      double cs = 0;
+      for (int d = 0; d < nx; ++d) {
+        const float w = W0[(size_t)h * n_in + 1 + d];
+        blob[oW1x + (size_t)h * nxp + d] = w;
+        blob[oW1xT + (size_t)d * H + h] = w;
+        cs += w;
+      }
+      blob[ow1t + h] = W0[(size_t)h * n_in];
+      blob[ob1 + h] = b0[h];
+      blob[oc1 + h] = (float)cs;
     }
-    const float *Wl[4] = {nullptr, nullptr, nullptr, nullptr}, *bl[4] = {nullptr, nullptr, nullptr, nullptr};
-    for (int l = 1; l < L; ++l) Wl[l] = blob.data() + oW[l], bl[l] = blob.data() + ob[l];
-    mlp_calibrate(nx, H, L, act, W0, b0, Wl, bl, ea, eb);
+    const float* cur = b0 + H;
+    for (int l = 1; l < L; ++l) {
+      oW[l] = take((size_t)H * H);
+      oWT[l] = take((size_t)H * H);
+      ob[l] = take(H);
+      for (int r = 0; r < H; ++r)
+        for (int c = 0; c < H; ++c) {
+          blob[oW[l] + (size_t)r * H + c] = cur[(size_t)r * H + c];
+          blob[oWT[l] + (size_t)c * H + r] = cur[(size_t)r * H + c];
+        }
+      cur += (size_t)H * H;
+      for (int h = 0; h < H; ++h) blob[ob[l] + h] = cur[h];
+      cur += H;
+    }
+    owout = take(H);
+    for (int h = 0; h < H; ++h) blob[owout + h] = cur[h];
+    bout = cur[H];
+    // fp16-split copies for the split MFMA path (H % 32 == 0)
+    if (H % 32 == 0) {
+      auto Wx = [&](int h, int d) { return d < nx ? W0[(size_t)h * n_in + 1 + d] : 0.f; };
+      oW1xS = pack_split(blob, H, nxp32, Wx);
+      oW1xTS = pack_split(blob, nxp32, H, [&](int d, int h) { return Wx(h, d); });
+      for (int l = 1; l < L; ++l) {
+        const float* Wl = blob.data() + oW[l];
+        std::vector<float> Wc(Wl, Wl + (size_t)H * H);
+        oWS[l] = pack_split(blob, H, H, [&](int r, int c) { return Wc[(size_t)r * H + c]; });
+        oWTS[l] = pack_split(blob, H, H, [&](int r, int c) { return Wc[(size_t)c * H + r]; });
+        oWU[l] = pack_split_x3(blob, H, H, [&](int r, int c) { return Wc[(size_t)r * H + c]; }, &wus[l]);
+      }
+      const float *Wl[4] = {nullptr, nullptr, nullptr, nullptr}, *bl[4] = {nullptr, nullptr, nullptr, nullptr};
+      for (int l = 1; l < L; ++l) Wl[l] = blob.data() + oW[l], bl[l] = blob.data() + ob[l];
+      mlp_calibrate(nx, H, L, act, W0, b0, Wl, bl, ea, eb);
+    }
   }
   auto* n = new dpi_net_s();
   std::memset(&n->d, 0, sizeof(n->d));
@@ -858,20 +902,31 @@ int dpi_net_create_mlp(int n_in, int n_hidden, const int* widths, int act, const
   n->d.L = L;
   n->d.nxp = nxp;
   n->d.act = act;
-  n->d.W1x = base + oW1x;
-  n->d.w1t = base + ow1t;
-  n->d.b1 = base + ob1;
-  n->d.c1 = base + oc1;
-  n->d.W1xT = base + oW1xT;
-  for (int l = 1; l < L; ++l) {
-    n->d.W[l] = base + oW[l];
-    n->d.WT[l] = base + oWT[l];
-    n->d.b[l] = base + ob[l];
+  n->spec = spec;
+  n->gen = gen;
+  if (gen) {
+    NetGen& g = n->g;
+    g.H = HC, g.L = L, g.nxp = nxg, g.act = act, g.ht = ((wmax + 31) & ~31) / 16;
+    g.W1x = base + gW1x, g.w1t = base + gw1t, g.b1 = base + gb1, g.c1 = base + gc1, g.W1xT = base + gW1xT;
+    for (int l = 1; l < L; ++l) g.W[l] = base + gW[l], g.WT[l] = base + gWT[l], g.b[l] = base + gb[l];
+    g.wout = base + gwout, g.bout = gbout;
   }
-  n->d.wout = base + owout;
-  n->d.bout = bout;
-  n->d.nxp32 = nxp32;
-  if (H % 32 == 0) {
+  if (spec) {
+    n->d.W1x = base + oW1x;
+    n->d.w1t = base + ow1t;
+    n->d.b1 = base + ob1;
+    n->d.c1 = base + oc1;
+    n->d.W1xT = base + oW1xT;
+    for (int l = 1; l < L; ++l) {
+      n->d.W[l] = base + oW[l];
+      n->d.WT[l] = base + oWT[l];
+      n->d.b[l] = base + ob[l];
+    }
+    n->d.wout = base + owout;
+    n->d.bout = bout;
+    n->d.nxp32 = nxp32;
+  }
+  if (spec && H % 32 == 0) {
     auto u32 = [&](size_t off) { return reinterpret_cast<const uint32_t*>(base + off); };
     n->d.W1xS = u32(oW1xS);
     n->d.W1xTS = u32(oW1xTS);
@@ -1229,9 +1284,9 @@ static int pis_chunk_wg() {
 }
 
 // Workspace: gx[n] | fb[n] | bx[n][H] | hb[n][HBS = 256] | tickets[n] | rec[n][BREC] | ready[n] |
-// [PIS rows] | partial[n][nbp][slab_row] | ...  (256-B aligned)
+// [PIS rows] | partial[n][nbp][slab_row] | ... | [stash]  (256-B aligned)
 struct WsLayout {
-  size_t gx, fb, bx, hb, tk, rec, ready, rows, partial, rq, noise, nq, total;
+  size_t gx, fb, bx, hb, tk, rec, ready, rows, partial, rq, noise, nq, stash, total;
   int rows_cap;
 };
 static size_t al256(size_t x) { return (x + 255) & ~size_t(255); }
@@ -1243,7 +1298,8 @@ static bool gbm_noise_prep(dpi_problem p, dpi_net net) {
 }
 static WsLayout ws_layout(dpi_net net, int n, int M, int F, bool noise = false) {
   WsLayout w;
-  const int H = (net && net->d.kind == 1) ? net->d.H : 0;
+  // bx rows: the specialised image's H, or the general one's width cap (the wider of the two)
+  const int H = (net && net->d.kind == 1) ? std::max(net->spec ? net->d.H : 0, net->gen ? net->g.H : 0) : 0;
   const size_t nbp = (size_t)(M + P - 1) / P;
   w.gx = 0;
   w.fb = al256((size_t)n * 4);
@@ -1270,6 +1326,13 @@ static WsLayout ws_layout(dpi_net net, int n, int M, int F, bool noise = false) 
   w.nq = w.noise + (noise ? al256((size_t)n * nbp * 2 * nb4 * P * 4) : 0);
   // k_noise_shared's queue counter (256 B) and per-SIMD claim words
   w.total = w.nq + (noise ? 256 + (size_t)PIS_CLAIM_SLOTS * 4 : 0);
+  // the general MLP family's stash (dpi_general.h): one slot per workgroup of its path launch, a fixed
+  // count — it does not grow with n or M.  The last region, so every other offset stays where it was.
+  w.stash = w.total;
+  if (net && net->d.kind == 1 && net->gen) {
+    w.stash = al256(w.total);
+    w.total = w.stash + al256((size_t)gen_slots(net->g.H) * gen_slot_floats(net->g.L, net->g.ht) * 4);
+  }
   return w;
 }
 
@@ -1567,7 +1630,34 @@ extern "C" int dpi_sample_points_t(dpi_problem p, int n, uint64_t seed, uint32_t
   return 0;
 }
 
+// Which k_paths family serves a (problem, net) pair: a pair with a specialised instance keeps it; any
+// other MLP net within the general family's caps runs that (it holds the general image then).
+static bool runs_general(const dpi_problem_s* p, const dpi_net_s* net) {
+  return net->d.kind == 1 && net->gen && !(net->spec && spec_shape(p->e.kind, net->d.H, net->d.L));
+}
+// The general family's refusals, each naming its cap.  td: the call uses the TD estimators.
+static int general_refusal(const dpi_problem_s* p, bool td, bool hess) {
+  const char* pre = "this network has no specialised kernel instance and the general MLP family (up to 8 hidden "
+                    "layers of width 256) ";
+  if (p->e.kind == DPI_EQ_GBM)
+    return fail(DPI_ERR_UNSUPPORTED, std::string(pre) + "serves Cha and OU problems only: GBM nets need one of its compiled "
+                                                        "shapes (widths <= 64, at most 3 hidden layers)");
+  if (hess) return fail(DPI_ERR_UNSUPPORTED, std::string(pre) + "has no Hessian labels");
+  if (p->e.nx > NXP_MAX)
+    return fail(DPI_ERR_UNSUPPORTED, std::string(pre) + "is compiled for nx <= 128 (NXP_MAX)");
+  if (td)
+    return fail(DPI_ERR_UNSUPPORTED, std::string(pre) + "has no TD estimators (ESTIMATE_DELTA_T > 0): those need at most "
+                                                        "4 hidden layers of width 128");
+  return 0;
+}
+
 static bool dispatch_any(const dpi_problem_s* p, const dpi_net_s* net, const Launch& q) {
+  if (q.gen) {  // the general MLP family (check_pair refused what it does not serve)
+    const bool tanh_g = !q.baseline && net->g.act == DPI_ACT_TANH;
+    for (const Unit& u : UNITS)
+      if (u.is(p->e.kind, false, tanh_g ? DPI_ACT_TANH : DPI_ACT_ELU, false, NXP_MAX, true)) return u.dispatch(p, net, q);
+    return false;
+  }
   // The unit's key (dpi_dispatch.h DPI_UNITS).  k_paths_fb (fused_base_ok) has ELU, non-TD, narrow
   // rows only, and GBM has none.  The baseline is shape- and activation-generic: it lives in the
   // plain ELU units whatever the net's activation, the problem's width or TD mode.  The wide
@@ -1600,6 +1690,12 @@ static Launch baseline_launch(const float* tx, int n, void* ws, const WsLayout& 
   q.st = st;
   return q;
 }
+// Routes a Launch of the pair to the general family where runs_general holds (path launches: with the
+// workspace's stash).
+static void route_launch(Launch& q, dpi_problem p, dpi_net net, void* ws, const WsLayout& w) {
+  q.gen = runs_general(p, net);
+  if (q.gen && !q.baseline) q.stash = (floatx4*)((char*)ws + w.stash);
+}
 static Launch path_launch(const PathArgs& a, int nblocks, hipStream_t st) {
   Launch q;
   q.a = &a;
@@ -1616,6 +1712,28 @@ static int check_pair(dpi_problem p, dpi_net net) {
   if (net->d.kind && net->d.nxp > NXW_MAX) return fail(DPI_ERR_ARG, "nx too large");
   if (p->e.nx > NXP_MAX && net->d.kind == 2)
     return fail(DPI_ERR_UNSUPPORTED, "PISGradNet: nx exceeds the compiled maximum state dimension 128 (NXP_MAX)");
+  if (runs_general(p, net)) return general_refusal(p, p->td_dt > 0.f, false);
+  return 0;
+}
+
+int dpi_pair_family(dpi_problem p, dpi_net net, int td, int* family) {
+  if (!p || !net || !family) return fail(DPI_ERR_ARG, "pair_family: null problem, net or family");
+  if (net->d.kind && net->n_in != 1 + p->e.nx) return fail(DPI_ERR_ARG, "net input width != 1 + nx");
+  *family = DPI_FAMILY_SPECIALISED;
+  if (net->d.kind != 1) return 0;
+  if (runs_general(p, net)) {
+    if (int rc = general_refusal(p, td != 0, false)) return rc;
+    *family = DPI_FAMILY_GENERAL;
+    return 0;
+  }
+  if (!spec_shape(p->e.kind, net->d.H, net->d.L))
+    return fail(DPI_ERR_UNSUPPORTED, "pair_family: unsupported equation/network shape");
+  return 0;
+}
+
+int dpi_general_slots(dpi_net net, int* slots) {
+  if (!net || !slots) return fail(DPI_ERR_ARG, "general_slots: null net or slots");
+  *slots = (net->d.kind == 1 && net->gen) ? gen_slots(net->g.H) : 0;
   return 0;
 }
 
@@ -1783,7 +1901,8 @@ int dpi_point_baseline(dpi_problem p, dpi_net net, const float* tx, int n, void*
   const WsLayout w = ws_layout(net, n, 0, 1 + p->e.nx);
   if (ws_bytes < w.partial) return fail(DPI_ERR_WORKSPACE, "workspace too small");
   if (net->d.kind == 2) return pis_baseline(p);
-  const Launch q = baseline_launch(tx, n, ws, w, (hipStream_t)stream);
+  Launch q = baseline_launch(tx, n, ws, w, (hipStream_t)stream);
+  route_launch(q, p, net, ws, w);
   if (!dispatch_any(p, net, q)) return fail(DPI_ERR_UNSUPPORTED, "point_baseline: unsupported equation/network shape");
   HIPCHK(hipGetLastError());
   base_tag_set(ws, n);
@@ -1809,6 +1928,7 @@ static int label_args(dpi_problem p, dpi_net net, const float* tx, int n, int M,
   const bool prepared = !need_moments || (flags & DPI_PREPARED);  // dpi_label_prepare, or its prepared call
   int rc = check_pair(p, net);
   if (rc) return rc;
+  if (hess && runs_general(p, net)) return general_refusal(p, false, true);
   if (hess && p->e.kind != DPI_EQ_GBM)
     return fail(DPI_ERR_UNSUPPORTED, "Hessian labels need a SimpleDiffusionEquationWithHessian (GBMEquationComplexExact)");
   if (hess && net->d.kind == 2) return fail(DPI_ERR_UNSUPPORTED, "Hessian labels: MLP or ZeroSolution networks only");
@@ -1896,6 +2016,7 @@ static int moments_impl(dpi_problem p, dpi_net net, const float* tx, int n, int 
     if ((rc = pis_paths(p, net, tx, n, K, a, w, b, st, (flags & DPI_PREPARED) != 0))) return rc;
   } else {
     Launch q = path_launch(a, n * nbp, st);
+    route_launch(q, p, net, ws, w);
     q.td = p->td_dt > 0.f;
     if (q.td && p->e.nx > NXP_MAX)
       return fail(DPI_ERR_UNSUPPORTED, "label_moments: the TD estimators (ESTIMATE_DELTA_T > 0) are compiled for "
@@ -1930,7 +2051,7 @@ static bool fused_base_on() { return env_int("DPI_FUSED_BASE", 1) != 0; }
 // (H % 32 == 0, the fused-MLP instances; not OU 4 x 128).  The run-time conditions on top: no TD,
 // nx <= NXP_MAX, and MLP nets in the fp16-split mode; the rest runs the two-launch form.
 static bool fused_base_ok(dpi_problem p, dpi_net net) {
-  if (p->td_dt > 0.f || p->e.nx > NXP_MAX) return false;
+  if (p->td_dt > 0.f || p->e.nx > NXP_MAX || runs_general(p, net)) return false;
   if (net->d.kind == 0) return fused_base_shape(p->e.kind, 0, 0, true, DPI_ACT_ELU);
   return net->d.kind == 1 && mlp_split(net) && fused_base_shape(p->e.kind, net->d.H, net->d.L, false, net->d.act);
 }
@@ -2015,6 +2136,7 @@ int dpi_sample_points_baseline(dpi_problem p, dpi_net net, int n, uint64_t seed,
   if (ws_bytes < w.partial) return fail(DPI_ERR_WORKSPACE, "workspace too small");
   Launch q = baseline_launch(tx, n, ws, w, (hipStream_t)stream);
   q.smp = sample_spec(p, seed, epoch, point_base, eps, t_factors, tx);
+  route_launch(q, p, net, ws, w);
   if (!dispatch_any(p, net, q))
     return fail(DPI_ERR_UNSUPPORTED, "sample_points_baseline: unsupported equation/network shape");
   HIPCHK(hipGetLastError());

@@ -1,0 +1,4 @@
+// The general MLP family (dpi_general.h), row gen_cha_tanh of DPI_UNITS.
+#include "dpi_dispatch.h"
+
+DPI_UNIT_DEFINE(gen_cha_tanh)

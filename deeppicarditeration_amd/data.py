@@ -327,7 +327,12 @@ class OnlineDataGenerator:
         self._scope = None  # the RangeGroup that label calls are deferred into (deferred_range_check)
         self._free_slots = list(range(UNCHECKED_SLOT - 1, IMMEDIATE_SLOT, -1))
         self._pending_slots = []  # (slot, event) of groups dropped unverified, until their kernels are done
-        self._fp32_fallback = False
+        # the general MLP family is exact fp32 whatever the precision mode: nothing to fall back to
+        # (a pair the label calls refuse: they say so themselves)
+        try:
+            self._fp32_fallback = self.net.family(self.problem, self.estimate_delta_t > 0) == _lib.DPI_FAMILY_GENERAL
+        except _lib.DPIError:
+            self._fp32_fallback = False
         # Points per generator call of the dataset surface (None: unbounded).  The reference sizes
         # its calls by probing GPU memory (picard/memory.py:95-171): a dataset whose calls exceed
         # this cap raises torch.cuda.OutOfMemoryError, which those probes read as "does not fit",

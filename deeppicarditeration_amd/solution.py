@@ -133,6 +133,21 @@ class DeviceNet:
         """Per-network GEMM precision (include/dpi.h dpi_net_set_precision; -1 = process-wide)."""
         _lib.check(_lib.load().dpi_net_set_precision(self.handle, int(mode)), "dpi_net_set_precision")
 
+    def general_slots(self):
+        """Stash slots of the general MLP family for this net (include/dpi.h dpi_general_slots); 0 for a
+        net that has a specialised first-order Cha / OU kernel instance."""
+        v = _lib.c_int(0)
+        _lib.check(_lib.load().dpi_general_slots(self.handle, _lib.ctypes.byref(v)), "dpi_general_slots")
+        return v.value
+
+    def family(self, problem, td=False):
+        """DPI_FAMILY_* the label calls on (problem, this net) run (include/dpi.h dpi_pair_family);
+        DPIError with the reason for a pair they would refuse."""
+        v = _lib.c_int(0)
+        _lib.check(_lib.load().dpi_pair_family(problem, self.handle, 1 if td else 0, _lib.ctypes.byref(v)),
+                   "dpi_pair_family")
+        return v.value
+
     def status(self, stream, clear=True):
         """The sticky DPI_STATUS_* word of the label reductions on this net (synchronises `stream`)."""
         v = _lib.c_int(0)
@@ -171,7 +186,12 @@ class DeviceNet:
             _lib.check(lib.dpi_net_create_mlp(n_in, len(widths), w, act_code,
                                               flat.ctypes.data_as(_lib.P(_lib.c_float)), flat.size, h),
                        "dpi_net_create_mlp")
-            return cls(h, f"mlp{widths}" + ("" if act_code == _lib.DPI_ACT_ELU else "-tanh"))
+            net = cls(h, f"mlp{widths}" + ("" if act_code == _lib.DPI_ACT_ELU else "-tanh"))
+            # no specialised first-order Cha / OU instance of this shape: those label calls run the
+            # general MLP family (exact fp32); with GBM only (width class 32, 3 layers) has an instance
+            if net.general_slots():
+                net.desc += "-general"
+            return net
         if isinstance(m, PISGradNet) or type(m).__name__ == "PISGradNet":
             return cls._from_pisgrad(lib, m, n_in)
         raise NotImplementedError(f"network type {type(m).__name__} has no device implementation in this build")

@@ -123,12 +123,29 @@ int dpi_problem_destroy(dpi_problem p);
 int dpi_net_create_zero(dpi_net* out);
 /* params: host fp32, torch state-dict order of construct_mlp(n_in, 1, widths, act):
  *   W0 (widths[0] x n_in), b0, W1 (widths[1] x widths[0]), b1, ..., Wout (1 x widths[-1]), bout.
- * Supported (width, n_hidden): all hidden widths equal, one of 16/32/64/128, n_hidden 1..4
- * (GBM: width <= 64).  act: the activation of every hidden layer, DPI_ACT_ELU (torch.nn.ELU,
- * alpha = 1) or DPI_ACT_TANH (torch.nn.Tanh, the reference's default NETWORK.ACTIVATIONS,
- * picard/config.py:61). */
+ * Supported: 1..8 hidden layers, each 1..256 wide (more of either: DPI_ERR_UNSUPPORTED).  The layers
+ * are zero-padded to a compiled width class H in {16, 32, 64, 128, 256} that holds the widest one.
+ * First-order Cha / OU labels (nx <= 128, no TD): every such net — a specialised kernel instance
+ * where (H, n_hidden) has one ((128, 2-4), (64, 2-3), (32, 2), (16, 1-3)), the general MLP family
+ * (exact fp32, run-time layer count) for every other pair.  GBM, the TD estimators, the Hessian
+ * labels and nx > 128 have the specialised instances only (GBM: (64, 2-3), (32, 2-3), (16, 1-3));
+ * any other net is refused at the label call with DPI_ERR_UNSUPPORTED (dpi_pair_family tells).
+ * act: the activation of every hidden layer, DPI_ACT_ELU (torch.nn.ELU, alpha = 1) or DPI_ACT_TANH
+ * (torch.nn.Tanh, the reference's default NETWORK.ACTIVATIONS, picard/config.py:61). */
 int dpi_net_create_mlp(int n_in, int n_hidden, const int* widths, int act, const float* params,
                        size_t n_params, dpi_net* out);
+/* Which kernel family the label calls on (p, net) run (host only, no device work): *family =
+ * DPI_FAMILY_SPECIALISED (also for zero and PISGradNet nets) or DPI_FAMILY_GENERAL, the general MLP
+ * family, which is fp32 only: dpi_set_gemm_precision / dpi_net_set_precision select nothing for it.
+ * td != 0: for the TD estimators (ESTIMATE_DELTA_T > 0).  DPI_ERR_UNSUPPORTED, with the reason in
+ * dpi_last_error, for a pair the label calls would refuse. */
+#define DPI_FAMILY_SPECIALISED 0
+#define DPI_FAMILY_GENERAL 1
+int dpi_pair_family(dpi_problem p, dpi_net net, int td, int* family);
+/* Workgroups of the general family's path launch on this net = slots of its stash, the region of
+ * the workspace where it parks one layer's act' per hidden layer (a fixed count: the stash does not
+ * grow with n or M); 0 for a net without the general image. */
+int dpi_general_slots(dpi_net net, int* slots);
 /* PISGradNet(hidden_shapes, dim = nx, g0 = equation.g, T) for OUProcessEquation; params: host fp32 in
  * torch state-dict order (timestep_phase, timestep_coeff, t_encoder.{0,2}, smooth_net.{0,2,..,2(L+1)},
  * nn_module.{0,2,..,2L} weights and biases).  Runs as an MFMA pipeline: rollout, time networks, the

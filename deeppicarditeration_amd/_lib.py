@@ -16,6 +16,7 @@ DPI_OK, DPI_ERR_ARG, DPI_ERR_UNSUPPORTED, DPI_ERR_HIP, DPI_ERR_WORKSPACE = 0, -1
 DPI_TAG_T, DPI_TAG_X0, DPI_TAG_X, DPI_TAG_TERM, DPI_TAG_S, DPI_TAG_INT, DPI_TAG_SDGD, DPI_TAG_HTERM, DPI_TAG_HINT = range(1, 10)
 DPI_EQ_CHA, DPI_EQ_OU, DPI_EQ_GBM = 1, 2, 3
 DPI_ACT_ELU, DPI_ACT_TANH = 1, 2
+DPI_HEAD_VALUE, DPI_HEAD_VALUE_GRADIENT, DPI_HEAD_GRADIENT = 0, 1, 2  # dpi_net_create_mlp_head
 DPI_TERMINAL, DPI_INTEGRAL, DPI_BOTH = 1, 2, 3
 DPI_PREPARED = 4  # dpi_label_moments: dpi_label_prepare already ran with the same arguments
 DPI_PATH_BLOCK = 64
@@ -43,6 +44,7 @@ SIGNATURES = {
     "dpi_problem_destroy": (c_int, [c_void_p]),
     "dpi_net_create_zero": (c_int, [P(c_void_p)]),
     "dpi_net_create_mlp": (c_int, [c_int, c_int, P(c_int), c_int, P(c_float), c_size_t, P(c_void_p)]),
+    "dpi_net_create_mlp_head": (c_int, [c_int, c_int, P(c_int), c_int, c_int, P(c_float), c_size_t, P(c_void_p)]),
     "dpi_net_create_pisgrad": (c_int, [c_int, c_int, P(c_int), c_double, P(c_float), c_size_t, P(c_void_p)]),
     "dpi_net_destroy": (c_int, [c_void_p]),
     "dpi_pair_family": (c_int, [c_void_p, c_void_p, c_int, P(c_int)]),

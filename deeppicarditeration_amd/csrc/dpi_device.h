@@ -2242,12 +2242,14 @@ constexpr int k_paths_wgs() {
 // NXW: the state-dimension cap of the instance (NXP_MAX; NXW_MAX for the wide first-order instances)
 // NET = NetGen: the general MLP family (k_paths_gen; H is its width cap HCAP, L unused — the net's
 // layer count is read at run time): phase 2 is mlp_tile_gen, gbid is the block index within the call
-// (the launch's first block + blockIdx.x) and stash the workgroup's stash slot.
+// (the launch's first block + blockIdx.x) and stash the workgroup's stash slot.  NET = NetGenHead: its
+// direct-gradient head form (k_paths_head): one launch over all blocks, no stash.
 template <int KIND, int H, int L, bool ZERO, bool SPLIT, bool HESS, bool TD, int ACT, bool FBT, int NXW = NXP_MAX,
           class NET = NetDev>
 __device__ __forceinline__ void paths_body(const EqDev& e, const NET& net, const PathArgs& a, const FusedBase& fb,
                                            unsigned gbid = 0u, floatx4* stash = nullptr) {
-  constexpr bool GEN = std::is_same_v<NET, NetGen>;
+  constexpr bool HEAD = std::is_same_v<NET, NetGenHead>;
+  constexpr bool GEN = std::is_same_v<NET, NetGen> || HEAD;
   static_assert(!GEN || (KIND != DPI_EQ_GBM && !ZERO && !SPLIT && !HESS && !TD && !FBT && NXW == NXP_MAX),
                 "the general family: first-order Cha / OU labels, exact fp32, nx <= 128");
   static_assert(!HESS || KIND == DPI_EQ_GBM, "Hessian labels: GBM (SimpleDiffusionEquationWithHessian) only");
@@ -2346,6 +2348,8 @@ __device__ __forceinline__ void paths_body(const EqDev& e, const NET& net, const
     if constexpr (GEN) {
       for (int l = 1; l < net.L; ++l)
         for (int h = tid; h < H; h += NTH) sh.bh[l * H + h] = net.b[l][h];
+      if constexpr (HEAD)  // bg in the unused layer-0 row (nxp up to 32 <= 128 <= H)
+        for (int d = tid; d < ((nxp + 31) & ~31); d += NTH) sh.bh[d] = net.bg[d];
     } else {
       for (int l = 1; l < L; ++l)
         for (int h = tid; h < H; h += NTH) sh.bh[l * H + h] = net.b[l][h];
@@ -2805,6 +2809,13 @@ __global__ __launch_bounds__(256, (gen_wgs(HCAP))) void k_paths_gen(EqDev e, Net
   floatx4* const slot = stash + (size_t)blockIdx.x * (gen_slot_floats(net.L, net.ht) / 4);
   paths_body<KIND, HCAP, GEN_LMAX, false, false, false, false, ACT, false, NXP_MAX, NetGen>(e, net, a, FusedBase{},
                                                                                              block0 + blockIdx.x, slot);
+}
+// The head form of the general family's path launch (dpi_general.h NetGenHead): every (point, 64-path
+// block) pair of the call in one launch — no stash, so no slot to own.
+template <int KIND, int HCAP, int ACT>
+__global__ __launch_bounds__(256, (gen_wgs(HCAP))) void k_paths_head(EqDev e, NetGenHead net, PathArgs a) {
+  paths_body<KIND, HCAP, GEN_LMAX, false, false, false, false, ACT, false, NXP_MAX, NetGenHead>(e, net, a, FusedBase{},
+                                                                                                 blockIdx.x, nullptr);
 }
 
 }  // namespace dpi

@@ -12,6 +12,13 @@
 // workgroup of one launch, not to a (point, block) pair: a call runs as consecutive k_paths_gen
 // launches of at most gen_slots(HCAP) blocks each on the call's stream, so the stash does not grow
 // with n M.
+//
+// Head nets (NetGenHead): a construct_mlp net whose last Linear outputs grad_x u directly — ValueGradient
+// (1 + nx outputs: u, grad u) or OnlyGradient (nx outputs: grad u; u = 0).  They need the forward pass
+// only: no act' stash, no backward loop, so no slot ownership — a call is one k_paths_head launch over
+// all its blocks.  The gradient block G (nx x H_last) of the last Linear is laid out as W1xT is, one
+// row per state dimension, and feeds the same gen_stage + gen_dot loop with a_L as the B operand; Cha,
+// which needs only sum_d u_x[d], takes it from cg = sum_d G[d] instead (two dots, no output GEMM).
 #pragma once
 
 namespace dpi {
@@ -41,6 +48,15 @@ struct NetGen {
   const float* b[GEN_LMAX];
   const float* wout;  // (H)
   float bout;
+};
+// A head net's image: NetGen's (the baseline's forward pass reads the transposed images), with the last
+// Linear split into the value row (wout, bout; ValueGradient only) and the gradient block.  c1 holds
+// cg[h] = sum_d G[d][h] (formed in fp64 at upload, as a value net's c1 is).
+struct NetGenHead : NetGen {
+  int value;        // 1: ValueGradient, u = wout . a_L + bout; 0: OnlyGradient, u = 0
+  const float* G;   // (nxp up to 32, H)   rows 1.. (ValueGradient) or 0.. (OnlyGradient) of the last Linear
+  const float* bg;  // (nxp up to 32)      their biases
+  float bgsum;      // sum_d bg[d]
 };
 // floats of one stash slot: act'(a_l) of layers 0..L-2, ht tiles of NTH float4 each
 __host__ __device__ constexpr size_t gen_slot_floats(int L, int ht) { return (size_t)(L - 1) * ht * NTH * 4; }
@@ -96,9 +112,11 @@ __device__ __forceinline__ floatx4 gen_dot(const float* wrow, const float (&b)[H
 // mlp_tile for a general net: same inputs (S tile, xsh, tau, cmul, vec, bh in LDS), outputs and tile
 // orientation (hidden x path, wave = 16 paths, exact-fp32 v_mfma_f32_16x16x4_f32).  stash: this
 // workgroup's slot.
-template <int KIND, int HCAP, int ACT>
-__device__ __forceinline__ void mlp_tile_gen(const EqDev& e, const NetGen& net, LdsGen<HCAP>& sh, floatx4* stash,
+// NET = NetGenHead: u and grad u are output columns (sh.bh[0 .. nxp) holds bg); stash is unused.
+template <int KIND, int HCAP, int ACT, class NET>
+__device__ __forceinline__ void mlp_tile_gen(const EqDev& e, const NET& net, LdsGen<HCAP>& sh, floatx4* stash,
                                              float& u_out, float& gsum_out, float& gA_out, float& gB_out) {
+  constexpr bool HEAD = std::is_same_v<NET, NetGenHead>;
   constexpr int HT = HCAP / 16, WS = LdsGen<HCAP>::WS, H = HCAP;
   static_assert(HT % 2 == 0, "tiles are taken in pairs");
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -144,11 +162,13 @@ __device__ __forceinline__ void mlp_tile_gen(const EqDev& e, const NetGen& net, 
   // ---------------- hidden layers; act'(a_l) of every layer but the last goes to the stash
 #pragma unroll 1
   for (int l = 1; l < L; ++l) {
+    if constexpr (!HEAD) {
 #pragma unroll
-    for (int T = 0; T < HT; ++T)
-      if (T < ht)
-        st[((l - 1) * ht + T) * NTH] = floatx4{Act<ACT>::d(a0[T][0]), Act<ACT>::d(a0[T][1]), Act<ACT>::d(a0[T][2]),
-                                               Act<ACT>::d(a0[T][3])};
+      for (int T = 0; T < HT; ++T)
+        if (T < ht)
+          st[((l - 1) * ht + T) * NTH] = floatx4{Act<ACT>::d(a0[T][0]), Act<ACT>::d(a0[T][1]), Act<ACT>::d(a0[T][2]),
+                                                 Act<ACT>::d(a0[T][3])};
+    }
     const float* const Wl = net.W[l];
     const float* const bl = sh.bh + l * H;
 #pragma unroll
@@ -169,6 +189,47 @@ __device__ __forceinline__ void mlp_tile_gen(const EqDev& e, const NetGen& net, 
     for (int T = 0; T < HT; ++T)
 #pragma unroll
       for (int r = 0; r < 4; ++r) a0[T][r] = a1[T][r];
+  }
+  if constexpr (HEAD) {
+    // ---------------- head: u = wout . a_L + bout (ValueGradient), grad u = G a_L + bg
+    float up = 0.f, gp = 0.f;
+#pragma unroll
+    for (int T = 0; T < HT; ++T)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int h = 16 * T + 4 * qq + r;
+        up = fmaf(sh.vec[2 * H + h], a0[T][r], up);
+        if (!Eq<KIND>::GRAD_FULL) gp = fmaf(sh.vec[3 * H + h], a0[T][r], gp);
+      }
+    u_out = net.value ? qsum(up) + net.bout : 0.f;
+    if (!Eq<KIND>::GRAD_FULL) {  // sum_d u_x[d] = cg . a_L + sum_d bg[d]
+      gsum_out = qsum(gp) + net.bgsum;
+      gA_out = gB_out = 0.f;
+    } else {
+      float A = 0.f, B = 0.f;
+#pragma unroll 1
+      for (int T0 = 0; T0 < nxt; T0 += 2) {
+        __syncthreads();
+        gen_stage<WS>(net.G, H, ncol, 16 * T0, sh.W);  // G has nxp rounded up to 32 rows
+        __syncthreads();
+#pragma unroll
+        for (int T2 = 0; T2 < 2; ++T2) {
+          const floatx4 acc = gen_dot<HT>(wrow + 16 * T2 * WS, a0, ht);
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int d = 16 * (T0 + T2) + 4 * qq + r;
+            if (d < e.nx) {
+              const float X = fmaf(cm, sh.S[d * SS + pp], sh.xsh[d]);
+              Eq<KIND>::gacc(e, d, X, acc[r] + sh.bh[d], A, B);
+            }
+          }
+        }
+      }
+      gA_out = qsum(A);
+      gB_out = qsum(B);
+      gsum_out = 0.f;
+    }
+    return;
   }
   // ---------------- output u = wout . a_L + bout ; delta_L = wout * act'(a_L)
   float up = 0.f;
@@ -266,10 +327,13 @@ __device__ __forceinline__ float gen_matvec(const float* __restrict__ Wt, const 
   }
   return y0 + y1;
 }
-template <int KIND>
-__global__ __launch_bounds__(NTB) void k_baseline_gen(EqDev e, NetGen net, const float* __restrict__ tx, int n,
-                                                     float* __restrict__ gx, float* __restrict__ fb,
-                                                     float* __restrict__ bx, SampleSpec smp, int* __restrict__ tickets) {
+// NET = NetGenHead (k_baseline_head): u and grad u at the point itself from the output columns.
+template <int KIND, class NET>
+__device__ __forceinline__ void baseline_gen_body(const EqDev& e, const NET& net, const float* __restrict__ tx, int n,
+                                                  float* __restrict__ gx, float* __restrict__ fb,
+                                                  float* __restrict__ bx, const SampleSpec& smp,
+                                                  int* __restrict__ tickets) {
+  constexpr bool HEAD = std::is_same_v<NET, NetGenHead>;
   static_assert(KIND != DPI_EQ_GBM, "the general family: Cha / OU");
   static_assert(NTB >= GEN_HMAX && NTB >= NXP_MAX, "one thread per hidden unit and per state dimension");
   constexpr int NT = NTB;
@@ -343,6 +407,26 @@ __global__ __launch_bounds__(NTB) void k_baseline_gen(EqDev e, NetGen net, const
     if (tid < H) bs.act[l][tid] = act_f(net.act, acc + net.b[l][tid]);
     __syncthreads();
   }
+  if constexpr (HEAD) {
+    const float* const aL = bs.act[L - 1];
+    const float u = net.value ? block_sum_n<NT>(tid < H ? net.wout[tid] * aL[tid] : 0.f, bs.red) + net.bout : 0.f;
+    float gs = 0.f, gA = 0.f, gB = 0.f;
+    if (!Eq<KIND>::GRAD_FULL) {
+      gs = block_sum_n<NT>(tid < H ? net.c1[tid] * aL[tid] : 0.f, bs.red) + net.bgsum;
+    } else {  // one wave per row of G (coalesced in the unit), rows in a fixed order
+      float A = 0.f, B = 0.f;
+      for (int d = tid >> 6; d < nx; d += NT / 64) {
+        float z = 0.f;
+        for (int k = tid & 63; k < hu; k += 64) z = fmaf(net.G[(size_t)d * H + k], aL[k], z);
+        z = wave_sum(z);
+        if ((tid & 63) == 0) Eq<KIND>::gacc(e, d, bs.xs[d], z + net.bg[d], A, B);
+      }
+      gA = block_sum_n<NT>(A, bs.red);
+      gB = block_sum_n<NT>(B, bs.red);
+    }
+    if (tid == 0) fb[i] = Eq<KIND>::ffv(e, u, gs, gA, gB);
+    return;
+  }
   const float u = block_sum_n<NT>(tid < H ? net.wout[tid] * bs.act[L - 1][tid] : 0.f, bs.red) + net.bout;
   int cur = 0;
   if (tid < H) bs.dbuf[0][tid] = net.wout[tid] * act_d(net.act, bs.act[L - 1][tid]);
@@ -367,6 +451,18 @@ __global__ __launch_bounds__(NTB) void k_baseline_gen(EqDev e, NetGen net, const
     gB = block_sum_n<NT>(B, bs.red);
   }
   if (tid == 0) fb[i] = Eq<KIND>::ffv(e, u, gs, gA, gB);  // state-dependent part
+}
+template <int KIND>
+__global__ __launch_bounds__(NTB) void k_baseline_gen(EqDev e, NetGen net, const float* __restrict__ tx, int n,
+                                                     float* __restrict__ gx, float* __restrict__ fb,
+                                                     float* __restrict__ bx, SampleSpec smp, int* __restrict__ tickets) {
+  baseline_gen_body<KIND>(e, net, tx, n, gx, fb, bx, smp, tickets);
+}
+template <int KIND>
+__global__ __launch_bounds__(NTB) void k_baseline_head(EqDev e, NetGenHead net, const float* __restrict__ tx, int n,
+                                                      float* __restrict__ gx, float* __restrict__ fb,
+                                                      float* __restrict__ bx, SampleSpec smp, int* __restrict__ tickets) {
+  baseline_gen_body<KIND>(e, net, tx, n, gx, fb, bx, smp, tickets);
 }
 
 }  // namespace dpi

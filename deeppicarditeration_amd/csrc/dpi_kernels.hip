@@ -952,6 +952,124 @@ int dpi_net_create_mlp(int n_in, int n_hidden, const int* widths, int act, const
   return 0;
 }
 
+// A gradient-head net (include/dpi.h): the general image only (dpi_general.h NetGenHead), whatever the
+// widths — built straight from the caller's rows with row stride HC, zero-padded as above.
+int dpi_net_create_mlp_head(int n_in, int n_hidden, const int* widths, int act, int head, const float* params,
+                            size_t n_params, dpi_net* out) {
+  if (head == DPI_HEAD_VALUE) return dpi_net_create_mlp(n_in, n_hidden, widths, act, params, n_params, out);
+  if (n_in - 1 > NXW_MAX)
+    return fail(DPI_ERR_UNSUPPORTED, "mlp: nx = n_in - 1 exceeds the compiled maximum state dimension 256 (NXW_MAX)");
+  if (!out || !widths || !params || n_in < 2 || n_hidden < 1) return fail(DPI_ERR_ARG, "mlp: bad arguments");
+  if (n_hidden > GEN_LMAX) return fail(DPI_ERR_UNSUPPORTED, "mlp: at most 8 hidden layers (GEN_LMAX)");
+  if (act != DPI_ACT_ELU && act != DPI_ACT_TANH)
+    return fail(DPI_ERR_UNSUPPORTED, "mlp: activations must be DPI_ACT_ELU or DPI_ACT_TANH");
+  if (head != DPI_HEAD_VALUE_GRADIENT && head != DPI_HEAD_GRADIENT)
+    return fail(DPI_ERR_ARG, "mlp_head: head must be DPI_HEAD_VALUE, DPI_HEAD_VALUE_GRADIENT or DPI_HEAD_GRADIENT");
+  const int nx = n_in - 1, L = n_hidden;
+  const bool value = head == DPI_HEAD_VALUE_GRADIENT;
+  const int n_out = value ? 1 + nx : nx;
+  int wmax = 0;
+  size_t expect = 0;
+  for (int l = 0; l < L; ++l) {
+    if (widths[l] < 1 || widths[l] > GEN_HMAX)
+      return fail(DPI_ERR_UNSUPPORTED, "mlp: hidden widths must be in [1, 256] (GEN_HMAX)");
+    wmax = std::max(wmax, widths[l]);
+    expect += (size_t)widths[l] * ((l ? widths[l - 1] : n_in) + 1);
+  }
+  const int wl = widths[L - 1];
+  expect += (size_t)n_out * (wl + 1);
+  if (n_params != expect)
+    return fail(DPI_ERR_ARG, value ? "mlp_head: parameter count mismatch (a ValueGradient head has 1 + nx output rows)"
+                                   : "mlp_head: parameter count mismatch (an OnlyGradient head has nx output rows)");
+  const int HC = wmax <= 128 ? 128 : 256, nxg = (nx + 15) & ~15, nxg32 = (nx + 31) & ~31;
+  std::vector<float> blob;
+  auto take = [&](size_t cnt) {
+    size_t off = blob.size();
+    blob.resize(off + ((cnt + 3) & ~size_t(3)), 0.f);
+    return off;
+  };
+  const size_t gW1x = take((size_t)HC * nxg), gw1t = take(HC), gb1 = take(HC), gW1xT = take((size_t)nxg32 * HC);
+  size_t gW[GEN_LMAX] = {0}, gWT[GEN_LMAX] = {0}, gb[GEN_LMAX] = {0};
+  const float* q = params;
+  for (int h = 0; h < widths[0]; ++h) {
+    for (int d = 0; d < nx; ++d) {
+      const float w = q[(size_t)h * n_in + 1 + d];
+      blob[gW1x + (size_t)h * nxg + d] = w;
+      blob[gW1xT + (size_t)d * HC + h] = w;
+    }
+    blob[gw1t + h] = q[(size_t)h * n_in];
+    blob[gb1 + h] = q[(size_t)widths[0] * n_in + h];
+  }
+  q += (size_t)widths[0] * (n_in + 1);
+  for (int l = 1; l < L; ++l) {
+    const int w = widths[l], win = widths[l - 1];
+    gW[l] = take((size_t)HC * HC), gWT[l] = take((size_t)HC * HC), gb[l] = take(HC);
+    for (int r = 0; r < w; ++r)
+      for (int c = 0; c < win; ++c) {
+        blob[gW[l] + (size_t)r * HC + c] = q[(size_t)r * win + c];
+        blob[gWT[l] + (size_t)c * HC + r] = q[(size_t)r * win + c];
+      }
+    q += (size_t)w * win;
+    for (int h = 0; h < w; ++h) blob[gb[l] + h] = q[h];
+    q += w;
+  }
+  // the last Linear: [value row |] nx gradient rows, then their biases; cg and sum bg in fp64
+  const size_t gwout = take(HC), gcg = take(HC), gG = take((size_t)nxg32 * HC), gbg = take(nxg32);
+  const float* const Wg = q + (value ? wl : 0);
+  const float* const bo = q + (size_t)n_out * wl;
+  for (int h = 0; h < wl; ++h) {
+    double cs = 0;
+    for (int d = 0; d < nx; ++d) {
+      const float w = Wg[(size_t)d * wl + h];
+      blob[gG + (size_t)d * HC + h] = w;
+      cs += w;
+    }
+    blob[gcg + h] = (float)cs;
+    if (value) blob[gwout + h] = q[h];
+  }
+  double bs = 0;
+  for (int d = 0; d < nx; ++d) {
+    blob[gbg + d] = bo[(value ? 1 : 0) + d];
+    bs += bo[(value ? 1 : 0) + d];
+  }
+  auto* n = new dpi_net_s();
+  std::memset(&n->d, 0, sizeof(n->d));
+  void* d = nullptr;
+  if (hipMalloc(&d, blob.size() * sizeof(float)) != hipSuccess) {
+    delete n;
+    return fail(DPI_ERR_HIP, "mlp_head: hipMalloc failed");
+  }
+  if (hipMemcpy(d, blob.data(), blob.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
+    (void)hipFree(d);
+    delete n;
+    return fail(DPI_ERR_HIP, "mlp_head: hipMemcpy failed");
+  }
+  const float* base = reinterpret_cast<const float*>(d);
+  n->blob = d;
+  n->n_in = n_in;
+  n->d.kind = 1;
+  n->d.H = HC;
+  n->d.L = L;
+  n->d.nxp = nxg;
+  n->d.act = act;
+  n->spec = false;
+  n->gen = true;
+  n->head = head;
+  NetGenHead& g = n->hd;
+  g.H = HC, g.L = L, g.nxp = nxg, g.act = act, g.ht = ((wmax + 31) & ~31) / 16;
+  g.W1x = base + gW1x, g.w1t = base + gw1t, g.b1 = base + gb1, g.c1 = base + gcg, g.W1xT = base + gW1xT;
+  for (int l = 1; l < L; ++l) g.W[l] = base + gW[l], g.WT[l] = base + gWT[l], g.b[l] = base + gb[l];
+  g.wout = base + gwout, g.bout = value ? bo[0] : 0.f;
+  g.value = value ? 1 : 0, g.G = base + gG, g.bg = base + gbg, g.bgsum = (float)bs;
+  n->g = g;  // the NetGen part: what the workspace layout and the routing read
+  if (int rc = net_init_status(n, params, n_params)) {
+    dpi_net_destroy(n);
+    return rc;
+  }
+  *out = n;
+  return 0;
+}
+
 int dpi_net_create_pisgrad(int nx, int n_hidden, const int* hidden, double T, const float* params, size_t n_params,
                            dpi_net* out) {
   if (nx > NXP_MAX)
@@ -1328,8 +1446,9 @@ static WsLayout ws_layout(dpi_net net, int n, int M, int F, bool noise = false) 
   w.total = w.nq + (noise ? 256 + (size_t)PIS_CLAIM_SLOTS * 4 : 0);
   // the general MLP family's stash (dpi_general.h): one slot per workgroup of its path launch, a fixed
   // count — it does not grow with n or M.  The last region, so every other offset stays where it was.
+  // A gradient-head net parks nothing: no stash region.
   w.stash = w.total;
-  if (net && net->d.kind == 1 && net->gen) {
+  if (net && net->d.kind == 1 && net->gen && !net->head) {
     w.stash = al256(w.total);
     w.total = w.stash + al256((size_t)gen_slots(net->g.H) * gen_slot_floats(net->g.L, net->g.ht) * 4);
   }
@@ -1636,7 +1755,19 @@ static bool runs_general(const dpi_problem_s* p, const dpi_net_s* net) {
   return net->d.kind == 1 && net->gen && !(net->spec && spec_shape(p->e.kind, net->d.H, net->d.L));
 }
 // The general family's refusals, each naming its cap.  td: the call uses the TD estimators.
-static int general_refusal(const dpi_problem_s* p, bool td, bool hess) {
+static int general_refusal(const dpi_problem_s* p, const dpi_net_s* net, bool td, bool hess) {
+  if (net->head) {  // a gradient head: the general family whatever its widths
+    const char* pre = "a ValueGradient / OnlyGradient network (a gradient head) runs the general MLP family, which ";
+    if (p->e.kind == DPI_EQ_GBM)
+      return fail(DPI_ERR_UNSUPPORTED, std::string(pre) + "serves Cha and OU problems only: GBM needs the Hessian of u, "
+                                                          "which a gradient head does not give");
+    if (hess) return fail(DPI_ERR_UNSUPPORTED, std::string(pre) + "has no Hessian labels");
+    if (p->e.nx > NXP_MAX)
+      return fail(DPI_ERR_UNSUPPORTED, std::string(pre) + "is compiled for nx <= 128 (NXP_MAX)");
+    if (td)
+      return fail(DPI_ERR_UNSUPPORTED, std::string(pre) + "has no TD estimators (ESTIMATE_DELTA_T > 0)");
+    return 0;
+  }
   const char* pre = "this network has no specialised kernel instance and the general MLP family (up to 8 hidden "
                     "layers of width 256) ";
   if (p->e.kind == DPI_EQ_GBM)
@@ -1654,8 +1785,11 @@ static int general_refusal(const dpi_problem_s* p, bool td, bool hess) {
 static bool dispatch_any(const dpi_problem_s* p, const dpi_net_s* net, const Launch& q) {
   if (q.gen) {  // the general MLP family (check_pair refused what it does not serve)
     const bool tanh_g = !q.baseline && net->g.act == DPI_ACT_TANH;
+    // head nets: the baseline unit, or the path unit of the image's width cap
+    const int head = !q.head ? 0 : q.baseline ? HEAD_BASE : net->g.H;
     for (const Unit& u : UNITS)
-      if (u.is(p->e.kind, false, tanh_g ? DPI_ACT_TANH : DPI_ACT_ELU, false, NXP_MAX, true)) return u.dispatch(p, net, q);
+      if (u.is(p->e.kind, false, tanh_g ? DPI_ACT_TANH : DPI_ACT_ELU, false, NXP_MAX, true, head))
+        return u.dispatch(p, net, q);
     return false;
   }
   // The unit's key (dpi_dispatch.h DPI_UNITS).  k_paths_fb (fused_base_ok) has ELU, non-TD, narrow
@@ -1694,7 +1828,8 @@ static Launch baseline_launch(const float* tx, int n, void* ws, const WsLayout& 
 // workspace's stash).
 static void route_launch(Launch& q, dpi_problem p, dpi_net net, void* ws, const WsLayout& w) {
   q.gen = runs_general(p, net);
-  if (q.gen && !q.baseline) q.stash = (floatx4*)((char*)ws + w.stash);
+  q.head = q.gen && net->head;
+  if (q.gen && !q.baseline && !q.head) q.stash = (floatx4*)((char*)ws + w.stash);
 }
 static Launch path_launch(const PathArgs& a, int nblocks, hipStream_t st) {
   Launch q;
@@ -1712,7 +1847,7 @@ static int check_pair(dpi_problem p, dpi_net net) {
   if (net->d.kind && net->d.nxp > NXW_MAX) return fail(DPI_ERR_ARG, "nx too large");
   if (p->e.nx > NXP_MAX && net->d.kind == 2)
     return fail(DPI_ERR_UNSUPPORTED, "PISGradNet: nx exceeds the compiled maximum state dimension 128 (NXP_MAX)");
-  if (runs_general(p, net)) return general_refusal(p, p->td_dt > 0.f, false);
+  if (runs_general(p, net)) return general_refusal(p, net, p->td_dt > 0.f, false);
   return 0;
 }
 
@@ -1722,7 +1857,7 @@ int dpi_pair_family(dpi_problem p, dpi_net net, int td, int* family) {
   *family = DPI_FAMILY_SPECIALISED;
   if (net->d.kind != 1) return 0;
   if (runs_general(p, net)) {
-    if (int rc = general_refusal(p, td != 0, false)) return rc;
+    if (int rc = general_refusal(p, net, td != 0, false)) return rc;
     *family = DPI_FAMILY_GENERAL;
     return 0;
   }
@@ -1733,7 +1868,7 @@ int dpi_pair_family(dpi_problem p, dpi_net net, int td, int* family) {
 
 int dpi_general_slots(dpi_net net, int* slots) {
   if (!net || !slots) return fail(DPI_ERR_ARG, "general_slots: null net or slots");
-  *slots = (net->d.kind == 1 && net->gen) ? gen_slots(net->g.H) : 0;
+  *slots = (net->d.kind == 1 && net->gen && !net->head) ? gen_slots(net->g.H) : 0;
   return 0;
 }
 
@@ -1928,7 +2063,7 @@ static int label_args(dpi_problem p, dpi_net net, const float* tx, int n, int M,
   const bool prepared = !need_moments || (flags & DPI_PREPARED);  // dpi_label_prepare, or its prepared call
   int rc = check_pair(p, net);
   if (rc) return rc;
-  if (hess && runs_general(p, net)) return general_refusal(p, false, true);
+  if (hess && runs_general(p, net)) return general_refusal(p, net, false, true);
   if (hess && p->e.kind != DPI_EQ_GBM)
     return fail(DPI_ERR_UNSUPPORTED, "Hessian labels need a SimpleDiffusionEquationWithHessian (GBMEquationComplexExact)");
   if (hess && net->d.kind == 2) return fail(DPI_ERR_UNSUPPORTED, "Hessian labels: MLP or ZeroSolution networks only");
@@ -2413,6 +2548,7 @@ int dpi_generate_with_gradients_and_hessians(dpi_problem p, dpi_net net, const f
                                              float* y, void* ws, size_t ws_bytes, void* stream) {
   int rc = check_pair(p, net);
   if (rc) return rc;
+  if (net->head) return general_refusal(p, net, false, true);  // a gradient head has no Hessian labels
   if (n < 0 || (!y && n) || M < 1 || M > 1024 * P)
     return fail(DPI_ERR_ARG, "generate_with_gradients_and_hessians: bad arguments (1 <= M <= 65536)");
   if (n == 0) return 0;

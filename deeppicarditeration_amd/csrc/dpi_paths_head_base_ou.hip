@@ -1,0 +1,4 @@
+// The head form of the general MLP family (dpi_general.h NetGenHead), row head_base_ou of DPI_UNITS.
+#include "dpi_dispatch.h"
+
+DPI_UNIT_DEFINE(head_base_ou)

@@ -6,6 +6,10 @@
 - `gradient_objective`: PicardSolutionGradientWrapper.training_step (picard/solution_jac.py:167-213)
   for a value network (output_dim 1): value loss plus the per-dimension gradient losses, combined
   by a loss scaler;
+- `head_gradient_objective`: the same training_step for a network that outputs the gradient
+  (solution_jac.py:184-194): ValueGradient (output_dim 1 + nx: value and gradient losses from the
+  output columns, optionally the aux loss tying the value column's own gradient to the gradient
+  columns) and OnlyGradient (output_dim nx: the value loss is 0);
 - `gradient_hessian_objective`: PicardSolutionGradientHessianWrapper.training_step
   (solution_jac.py:219-259), plus the Hessian losses (all nx^2 entries, or NUM_HESS_SAMPLES of them
   drawn with `random.sample` as there);
@@ -13,7 +17,8 @@
 - `build_objective`: the wrapper choice of PicardRunner.get_solution (picard_iteration.py:113-118)
   and PicardSolutionGradientWrapper.construct_solution / __init__ (solution_jac.py:112-136).
 
-Each objective is `f(net, tx, y) -> (loss (1,), info dict)`; `net` maps tx (B, 1+nx) -> (B, 1).
+Each objective is `f(net, tx, y) -> (loss (1,), info dict)`; `net` maps tx (B, 1+nx) -> (B, 1), or
+(B, 1+nx) / (B, nx) for the head objectives.
 """
 import random
 
@@ -122,14 +127,15 @@ def _weight(tx, beta):
     return torch.exp(torch.narrow(tx, -1, 0, 1) * beta)
 
 
-def _u_and_grad(net, tx):
+def _u_and_grad(net, tx, column0=False):
     """u (B, 1) and d u / d tx (B, 1+nx) — the per-row Jacobian of a value network (the reference's
     vmap(jacrev(forward)), solution_jac.py:121), as one reverse pass over the batch sum with the
-    graph kept for the parameter gradient."""
+    graph kept for the parameter gradient.  column0: the network has more outputs and u is its
+    column 0 (solution_only_u, solution_jac.py:163-165); the whole output is returned."""
     tx = tx.detach().requires_grad_(True)
     with torch.enable_grad():
         u = net(tx)
-        (u_tx,) = torch.autograd.grad(u.sum(), tx, create_graph=True)
+        (u_tx,) = torch.autograd.grad((u[:, 0] if column0 else u).sum(), tx, create_graph=True)
     return u, u_tx
 
 
@@ -147,6 +153,39 @@ def gradient_objective(beta, loss_fn, scaler, nx):
         v_loss = torch.mean(w * loss_fn(u - y[:, :1]), dim=0)
         g_loss = torch.mean(w * loss_fn(u_tx[:, 1:] - y[:, 1:1 + nx]), dim=0)
         loss, info = scaler.scale(v_loss, g_loss)
+        info["train_value_loss"] = v_loss
+        return loss, info
+    return objective
+
+
+def head_gradient_objective(beta, loss_fn, scaler, nx, output_dim, use_aux_loss=False, weight_aux_loss=0.0):
+    """solution_jac.py:184-213 for output_dim nx (OnlyGradient) and 1 + nx (ValueGradient).  The aux
+    loss (ValueGradient only) is the unweighted mean of loss_fn(d out[:, 0] / dx - out[:, 1:]), added
+    per dimension to the gradient loss with weight_aux_loss."""
+    if output_dim not in (nx, 1 + nx) or output_dim == 1:
+        raise ValueError(f"head_gradient_objective: output_dim {output_dim} is neither nx = {nx} nor 1 + nx")
+    only = output_dim == nx
+
+    def objective(net, tx, y):
+        w = _weight(tx, beta)
+        info = {}
+        if only:
+            u_x = net(tx)
+            v_loss = torch.zeros(1, device=tx.device, dtype=tx.dtype)
+        else:
+            if use_aux_loss:
+                out, u_tx = _u_and_grad(net, tx, column0=True)
+                aux = torch.mean(loss_fn(u_tx[:, 1:] - out[:, 1:]), dim=0)
+            else:
+                out = net(tx)
+            u, u_x = out[:, 0:1], out[:, 1:]
+            v_loss = torch.mean(w * loss_fn(u - y[:, :1]), dim=0)
+        g_loss = torch.mean(w * loss_fn(u_x - y[:, 1:1 + nx]), dim=0)
+        if use_aux_loss and not only:
+            g_loss = g_loss + weight_aux_loss * aux
+            info["aux_loss"] = aux.mean(dim=-1)
+        loss, sinfo = scaler.scale(v_loss, g_loss)
+        info.update(sinfo)
         info["train_value_loss"] = v_loss
         return loss, info
     return objective
@@ -177,18 +216,37 @@ def make_scaler(scaler_cfg):
     return LossScaler.get_class(scaler_cfg["cls"])(**dict(scaler_cfg.get("kwargs") or {}))
 
 
-def build_objective(train_cfg, nx, supervise_gradient, supervise_hessian):
+def build_objective(train_cfg, nx, supervise_gradient, supervise_hessian, output_dim=1):
     """PicardRunner.get_solution (picard_iteration.py:113-118) + the wrappers' construct_solution
     (solution_jac.py:112-119): returns (objective, kind) with kind in {"value", "gradient",
-    "gradient_hessian"}.  A FixedLossScaler of weight <= 1e-9 falls back to the plain value fit."""
+    "gradient_hessian", "head_value_gradient", "head_only_gradient"}.  output_dim: the network's
+    output width (1: a Value net; 1 + nx / nx: a ValueGradient / OnlyGradient head).  A
+    FixedLossScaler of weight <= 1e-9 falls back to the plain value fit (Value nets)."""
     loss_cfg = train_cfg["LOSS"]
     beta = float(loss_cfg["beta"])
     loss_fn = make_loss_fn(loss_cfg.get("FN"))
+    head = output_dim != 1
+    if head and output_dim not in (nx, 1 + nx):
+        raise ValueError(f"network output width {output_dim}: must be 1, 1 + nx = {1 + nx} or nx = {nx}")
+    if head and supervise_hessian:
+        raise NotImplementedError("TRAIN.SUPERVISE_HESSIAN with a ValueGradient / OnlyGradient network: Hessian "
+                                  "supervision of a gradient head is out of scope")
+    if head and not supervise_gradient:
+        raise NotImplementedError("a ValueGradient / OnlyGradient network is fitted to gradient labels: set "
+                                  "TRAIN.SUPERVISE_GRADIENT (or use an equation with a gradient term)")
     if not (supervise_gradient or supervise_hessian):
         return value_objective(beta, loss_fn), "value"
-    if loss_cfg.get("use_aux_loss"):
+    aux = bool(loss_cfg.get("use_aux_loss"))
+    if aux and output_dim != 1 + nx:
         raise NotImplementedError("TRAIN.LOSS.use_aux_loss applies to ValueGradient networks only")
     scaler = make_scaler(loss_cfg.get("SCALER"))
+    if head:
+        if isinstance(scaler, FixedLossScaler) and scaler.fixed_weight <= 1e-9:
+            raise NotImplementedError("FixedLossScaler fixed_weight <= 1e-9 with a ValueGradient / OnlyGradient network: "
+                                      "the plain value fit it selects has no meaning for a gradient head")
+        obj = head_gradient_objective(beta, loss_fn, scaler, nx, output_dim, aux,
+                                      float(loss_cfg.get("weight_aux_loss") or 0.0))
+        return obj, "head_only_gradient" if output_dim == nx else "head_value_gradient"
     if isinstance(scaler, FixedLossScaler) and scaler.fixed_weight <= 1e-9:
         return value_objective(beta, loss_fn), "value"
     if supervise_hessian:

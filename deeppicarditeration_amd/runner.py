@@ -29,7 +29,7 @@ from .data import OnlineDataGenerator
 from .dataset import TensorDatasetBuiltInShuffle
 from .fit import build_objective, make_optimizer, train_steps
 from .sharding import ShardedLabeler
-from .solution import PISGradNet, ZeroSolution, construct_mlp
+from .solution import OUTPUT_DIM, PISGradNet, ZeroSolution, construct_mlp, head_columns
 
 
 class LabelBuffer:
@@ -130,11 +130,20 @@ class PicardRunner:
         self.equation = getattr(eqs, cfg.EQUATION.cls)(**cfg.EQUATION.kwargs)  # picard_iteration.py:90-92
         self.supervise_gradient = bool(cfg.TRAIN.SUPERVISE_GRADIENT or self.equation.has_gradient_term)
         self.supervise_hessian = bool(cfg.TRAIN.SUPERVISE_HESSIAN)  # picard_iteration.py:160, :114
-        if cfg.NETWORK.TYPE != "Value":
-            raise NotImplementedError("NETWORK.TYPE must be 'Value' for the device label path")
+        # NETWORK.TYPE (picard/solution.py:304-311, picard_iteration.py:170-182): the output width of
+        # the network and of the ZeroSolution the loop starts from
+        if cfg.NETWORK.TYPE not in OUTPUT_DIM:
+            raise ValueError(f"Unknown network type {cfg.NETWORK.TYPE}")
+        self.output_dim = OUTPUT_DIM[cfg.NETWORK.TYPE](self.equation.nx)
+        if cfg.NETWORK.PISGRADNET and cfg.NETWORK.TYPE != "Value":
+            raise NotImplementedError(f"NETWORK.PISGRADNET with NETWORK.TYPE={cfg.NETWORK.TYPE}: PISGradNet is a "
+                                      "Value network")
+        if self.output_dim != 1 and self.supervise_hessian:
+            raise NotImplementedError(f"TRAIN.SUPERVISE_HESSIAN with NETWORK.TYPE={cfg.NETWORK.TYPE}: Hessian labels "
+                                      "and Hessian supervision of a gradient head are out of scope")
         self.N = cfg.PICARD.N
         self.i = 0
-        self.u_current = ZeroSolution(1)
+        self.u_current = ZeroSolution(self.output_dim)
         self.history = []
 
     def _agree(self, err, what):
@@ -158,7 +167,7 @@ class PicardRunner:
         if c.PISGRADNET:  # picard/solution.py:313-316
             net = PISGradNet(hidden_shapes=list(c.NEURONS), dim=self.equation.nx, g0=self.equation.g, T=self.equation.T)
         else:
-            net = construct_mlp(1 + self.equation.nx, 1, list(c.NEURONS), list(c.ACTIVATIONS), c.BOUND)
+            net = construct_mlp(1 + self.equation.nx, self.output_dim, list(c.NEURONS), list(c.ACTIVATIONS), c.BOUND)
         return net.to(self.device)
 
     def checkpoint_path(self, i):
@@ -200,7 +209,7 @@ class PicardRunner:
         replay the in-memory cache, shuffled when DATA.SHUFFLE is set (dataset.py:203-255)."""
         t = self.cfg.TRAIN
         objective, self.fit_kind = build_objective(t, self.equation.nx, self.supervise_gradient,
-                                                   self.supervise_hessian)
+                                                   self.supervise_hessian, self.output_dim)
         opt, sched = make_optimizer(net.parameters(), t.OPTIMIZER)
         n = tx.shape[0]
         bs = int(t.BATCH_SIZE) if t.BATCH_SIZE else n
@@ -224,7 +233,9 @@ class PicardRunner:
         """EvalCallback (picard/utils.py:329-478): at t = linspace(0, T, n) and x = equation.sample_x(t)
         (seeded per iteration), u of the network vs the exact solution; with EVAL.TEST_GRAD the
         gradient errors and with EVAL.TEST_HESSIAN the Hessian errors (at most 256 points for the
-        nx^2 Hessians).  Returns the metrics dict, or {} when the equation has no exact solution."""
+        nx^2 Hessians).  A ValueGradient / OnlyGradient network is scored on its output columns, value
+        and gradient both (compute_at_t_valuegrad / compute_at_t_onlygrad, utils.py:231-327, :388-401).
+        Returns the metrics dict, or {} when the equation has no exact solution."""
         import numpy as np
         ev = self.cfg.EVAL
         n = int(n_points or ev.L2_N_POINTS)
@@ -239,6 +250,11 @@ class PicardRunner:
             return {}
         dt = next(net.parameters()).dtype if any(True for _ in net.parameters()) else torch.float32
         tx = torch.cat([t, x], -1).to(device=self.device, dtype=dt)
+        if self.output_dim != 1:
+            with torch.no_grad():
+                u, ux = head_columns(net(tx), eq.nx)
+            return eval_metrics(u.double().cpu().numpy(), u_exact.numpy(), ux.double().cpu().numpy(),
+                                eq.u_x(t, x).detach().numpy())
         grads = bool(ev.TEST_GRAD)
         with torch.enable_grad() if grads else torch.no_grad():
             if grads:

@@ -116,6 +116,37 @@ def _unwrap(module):
         module = inner
 
 
+HEAD_NAMES = {_lib.DPI_HEAD_VALUE: "Value", _lib.DPI_HEAD_VALUE_GRADIENT: "ValueGradient",
+              _lib.DPI_HEAD_GRADIENT: "OnlyGradient"}
+# NETWORK.TYPE -> the network's output width (picard/solution.py:301-324)
+OUTPUT_DIM = {"Value": lambda nx: 1, "ValueGradient": lambda nx: 1 + nx, "OnlyGradient": lambda nx: nx}
+
+
+def head_of(n_out: int, nx: int) -> int:
+    """The DPI_HEAD_* of a network with n_out outputs on an nx-dimensional problem, by the reference's
+    rule (picard/data.py:1231-1242): 1 is a Value net, 1 + nx a ValueGradient net (u = out[:, 0],
+    u_x = out[:, 1:]), nx an OnlyGradient net (u_x = out, u = 0)."""
+    if n_out == 1:
+        return _lib.DPI_HEAD_VALUE
+    if n_out == 1 + nx:
+        return _lib.DPI_HEAD_VALUE_GRADIENT
+    if n_out == nx:
+        return _lib.DPI_HEAD_GRADIENT
+    raise ValueError(f"network output width {n_out}: must be 1 (Value), 1 + nx = {1 + nx} (ValueGradient) or "
+                     f"nx = {nx} (OnlyGradient)")
+
+
+def head_columns(out, nx: int):
+    """(u, u_x) of a network output `out` (B, n_out): the columns get_f reads (picard/data.py:1231-1242);
+    u_x is None for a Value net (it is differentiated instead)."""
+    head = head_of(out.shape[-1], nx)
+    if head == _lib.DPI_HEAD_VALUE:
+        return out, None
+    if head == _lib.DPI_HEAD_VALUE_GRADIENT:
+        return out[..., 0:1], out[..., 1:]
+    return out[..., 0:1] * 0, out
+
+
 class DeviceNet:
     """A network uploaded to the label kernels (owns a dpi_net handle)."""
 
@@ -174,15 +205,21 @@ class DeviceNet:
                                           "all-Tanh hidden layers")
             if any(l.alpha != 1.0 for l in m if isinstance(l, torch.nn.ELU)):
                 raise NotImplementedError("ELU alpha != 1")
-            if lin[-1].out_features != 1:
-                raise NotImplementedError("network output_dim != 1 (Value networks only)")
             if lin[0].in_features != n_in:
                 raise ValueError(f"network input {lin[0].in_features} != 1 + nx = {n_in}")
+            head = head_of(lin[-1].out_features, n_in - 1)
             widths = [l.out_features for l in lin[:-1]]
             flat = np.concatenate([np.concatenate([l.weight.detach().cpu().double().numpy().ravel(),
                                                    l.bias.detach().cpu().double().numpy().ravel()]) for l in lin])
             flat = np.ascontiguousarray(flat, np.float32)
             w = (_lib.c_int * len(widths))(*widths)
+            if head != _lib.DPI_HEAD_VALUE:
+                # a gradient head (NETWORK.TYPE ValueGradient / OnlyGradient): grad u is an output, the
+                # labels run the general family's forward-only head kernels whatever the widths
+                _lib.check(lib.dpi_net_create_mlp_head(n_in, len(widths), w, act_code, head,
+                                                       flat.ctypes.data_as(_lib.P(_lib.c_float)), flat.size, h),
+                           "dpi_net_create_mlp_head")
+                return cls(h, f"mlp{widths}" + ("" if act_code == _lib.DPI_ACT_ELU else "-tanh") + "-" + HEAD_NAMES[head])
             _lib.check(lib.dpi_net_create_mlp(n_in, len(widths), w, act_code,
                                               flat.ctypes.data_as(_lib.P(_lib.c_float)), flat.size, h),
                        "dpi_net_create_mlp")

@@ -17,6 +17,7 @@
  *   dpi_problem_set_estimate_delta_t  picard/data.py:1209-1213, :934-952, :529-575  ESTIMATE_DELTA_T (TD estimators)
  *   dpi_net_create_zero      picard/solution.py:330-337   ZeroSolution (iteration 1)
  *   dpi_net_create_mlp       picard/solution.py:123-135   construct_mlp (state-dict order)
+ *   dpi_net_create_mlp_head  picard/solution.py:301-324, picard/data.py:1231-1242  NETWORK.TYPE ValueGradient / OnlyGradient
  *   dpi_net_create_pisgrad   picard/solution.py:138-289   PISGradNet (state-dict order)
  *   dpi_sample_points        picard/data.py:161-167, :211-217  sample_t_always_uniform + equation.sample_x
  *   dpi_sample_points_t      picard/data.py:149-159 (sample_t, t_always_uniform: false) or :161-167
@@ -134,6 +135,22 @@ int dpi_net_create_zero(dpi_net* out);
  * (torch.nn.Tanh, the reference's default NETWORK.ACTIVATIONS, picard/config.py:61). */
 int dpi_net_create_mlp(int n_in, int n_hidden, const int* widths, int act, const float* params,
                        size_t n_params, dpi_net* out);
+/* construct_mlp(n_in, n_out, widths, act) with the head NETWORK.TYPE selects (picard/solution.py:301-324,
+ * picard/data.py:1231-1242): the last Linear's n_out rows are
+ *   DPI_HEAD_VALUE           n_out = 1         u                (dpi_net_create_mlp itself)
+ *   DPI_HEAD_VALUE_GRADIENT  n_out = n_in      u, grad_x u      (ValueGradient)
+ *   DPI_HEAD_GRADIENT        n_out = n_in - 1  grad_x u; u = 0  (OnlyGradient)
+ * params as above with Wout (n_out x widths[-1]), bout (n_out); n_params must match the head's n_out
+ * (DPI_ERR_ARG), an unknown head code is DPI_ERR_ARG, the caps are dpi_net_create_mlp's.  A gradient
+ * head outputs grad_x u instead of having it differentiated: its labels need the forward pass only
+ * and run the general MLP family whatever the widths (first-order Cha / OU labels, nx <= 128, no TD;
+ * GBM, the TD estimators, Hessian labels and nx > 128 are refused at the label call and by
+ * dpi_pair_family with DPI_ERR_UNSUPPORTED).  Its workspace has no stash. */
+#define DPI_HEAD_VALUE 0
+#define DPI_HEAD_VALUE_GRADIENT 1
+#define DPI_HEAD_GRADIENT 2
+int dpi_net_create_mlp_head(int n_in, int n_hidden, const int* widths, int act, int head, const float* params,
+                            size_t n_params, dpi_net* out);
 /* Which kernel family the label calls on (p, net) run (host only, no device work): *family =
  * DPI_FAMILY_SPECIALISED (also for zero and PISGradNet nets) or DPI_FAMILY_GENERAL, the general MLP
  * family, which is fp32 only: dpi_set_gemm_precision / dpi_net_set_precision select nothing for it.
@@ -144,7 +161,7 @@ int dpi_net_create_mlp(int n_in, int n_hidden, const int* widths, int act, const
 int dpi_pair_family(dpi_problem p, dpi_net net, int td, int* family);
 /* Workgroups of the general family's path launch on this net = slots of its stash, the region of
  * the workspace where it parks one layer's act' per hidden layer (a fixed count: the stash does not
- * grow with n or M); 0 for a net without the general image. */
+ * grow with n or M); 0 for a net without the general image and for a gradient-head net (no stash). */
 int dpi_general_slots(dpi_net net, int* slots);
 /* PISGradNet(hidden_shapes, dim = nx, g0 = equation.g, T) for OUProcessEquation; params: host fp32 in
  * torch state-dict order (timestep_phase, timestep_coeff, t_encoder.{0,2}, smooth_net.{0,2,..,2(L+1)},

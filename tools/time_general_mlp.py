@@ -4,8 +4,9 @@ The Burgers bench shape — Cha, nx = 100, 16 points x 4,096 paths, K = 50 — o
 sample_with_gradients (points, per-point baseline, path launches, reduce).  Per net: warm-up calls,
 then REPS calls each bracketed by its own pair of HIP events; the median is reported (ms/step), with
 the minimum beside it.  The yardstick is the specialised 4 x 128 instance in both precision modes,
-in the same process on the same device; then the general 4 x 64, 5 x 128, 8 x 128, 4 x 256, 8 x 256.
-One JSON line per net, and the LDS / register / workgroups-per-CU figures of the general kernels
+in the same process on the same device; then the general 4 x 64, 5 x 128, 8 x 128, 4 x 256, 8 x 256,
+and the gradient-head nets (NETWORK.TYPE ValueGradient / OnlyGradient) 4 x 128 and
+8 x 256, which run the general family's forward-only head kernels.  One JSON line per net, and the LDS / register / workgroups-per-CU figures of the general kernels
 from the library's code objects.
 
     python tools/time_general_mlp.py [--reps 30] [--warmup 5] [--act ELU]
@@ -25,19 +26,24 @@ from deeppicarditeration_amd.build import kernel_resources  # noqa: E402
 NX, N, M, K = 100, 16, 4096, 50
 NETS = [("specialised 4x128 fp16-split", [128] * 4, L.DPI_GEMM_AUTO), ("specialised 4x128 fp32", [128] * 4, L.DPI_GEMM_F32),
         ("general 4x64", [64] * 4, None), ("general 5x128", [128] * 5, None), ("general 8x128", [128] * 8, None),
-        ("general 4x256", [256] * 4, None), ("general 8x256", [256] * 8, None)]
+        ("general 4x256", [256] * 4, None), ("general 8x256", [256] * 8, None),
+        ("head 4x128 ValueGradient", [128] * 4, None, 1 + NX), ("head 4x128 OnlyGradient", [128] * 4, None, NX),
+        ("head 8x256 ValueGradient", [256] * 8, None, 1 + NX), ("head 8x256 OnlyGradient", [256] * 8, None, NX)]
 
 
-def mlp_flops(widths):
-    """Forward + backward MACs x 2 per path of the padded network phase (layer 1 over nx)."""
+def mlp_flops(widths, n_out=1):
+    """Forward + backward MACs x 2 per path of the padded network phase (layer 1 over nx); a gradient
+    head (n_out > 1): the forward MACs and the output rows (Cha reads only their sum: two dots)."""
+    if n_out > 1:
+        return 2 * (NX * widths[0] + sum(a * b for a, b in zip(widths[:-1], widths[1:])) + 2 * widths[-1])
     f = 2 * NX * widths[0] + sum(2 * 2 * a * b for a, b in zip(widths[:-1], widths[1:]))
     return 2 * f
 
 
-def time_net(widths, mode, act, reps, warmup):
+def time_net(widths, mode, act, reps, warmup, n_out=1):
     torch.manual_seed(0)
     eq = dpi.Cha(NX, 1.0, 5.0, 1.0)
-    net = dpi.construct_mlp(1 + NX, 1, widths, [act] * len(widths), None)
+    net = dpi.construct_mlp(1 + NX, n_out, widths, [act] * len(widths), None)
     gen = dpi.OnlineDataGenerator(eq, net, 1, 1, device="cuda:0", t_always_uniform=True, n_estimate_terminal=M,
                                   n_estimate_integral=M, n_euler_steps=K, seed=5)
     if mode is not None:
@@ -57,7 +63,7 @@ def time_net(widths, mode, act, reps, warmup):
     torch.cuda.synchronize()
     t = sorted(a.elapsed_time(b) for a, b in evs)
     return {"family": "general" if family == L.DPI_FAMILY_GENERAL else "specialised", "ms_median": t[len(t) // 2],
-            "ms_min": t[0], "mlp_mflop_per_path": mlp_flops(widths) / 1e6, "stash_slots": gen.net.general_slots(),
+            "ms_min": t[0], "mlp_mflop_per_path": mlp_flops(widths, n_out) / 1e6, "stash_slots": gen.net.general_slots(),
             "workspace_mb": gen.workspace_bytes(N, M) / 2 ** 20}
 
 
@@ -69,12 +75,13 @@ def main():
     a = ap.parse_args()
     assert a.reps >= 20, "the median of at least 20 calls"
     for k in kernel_resources():
-        if "k_paths_gen<" in k["name"] or "k_baseline_gen<" in k["name"]:
+        if any(f in k["name"] for f in ("k_paths_gen<", "k_baseline_gen<", "k_paths_head<", "k_baseline_head<")):
             print(json.dumps({"kernel": k["name"].split("(")[0], "vgpr": k["vgpr_count"], "agpr": k["agpr_count"],
                               "lds_bytes": k["group_segment_fixed_size"], "sgpr_spill": k["sgpr_spill_count"],
                               "vgpr_spill": k["vgpr_spill_count"]}), flush=True)
-    for name, widths, mode in NETS:
-        print(json.dumps({"net": name, "act": a.act, **time_net(widths, mode, a.act, a.reps, a.warmup)}), flush=True)
+    for name, widths, mode, *n_out in NETS:
+        print(json.dumps({"net": name, "act": a.act, **time_net(widths, mode, a.act, a.reps, a.warmup, *n_out)}),
+              flush=True)
 
 
 if __name__ == "__main__":

@@ -11,7 +11,11 @@ Shapes: n = 3 points, M = 128 paths (two 64-path blocks per point, so the cross-
 K = 2 Euler steps; nx = 7 on the narrow rows (no multiple of 4 or 16: the padding lanes are live)
 and 129 on the wide ones (the first width past NXP_MAX = 128); TD rows at estimate_delta_t = 0.3,
 where the three uniform times fall on both sides of t + dt < T; GBM with the full Hessian diagonal
-(no SDGD).  Tolerance: the suite's rel-L2 < 1e-4 on the value column and on the gradient block."""
+(no SDGD).  Tolerance: the suite's rel-L2 < 1e-4 on the value column and on the gradient block.
+
+These nets stand at torch's default initialisation, where the network adds 1e-5 .. 1e-2 of the label:
+tests/test_gpu_network_phase.py runs the same rows with nets whose share of the label is gated on the
+CPU, and is the test that is sensitive to the network phase."""
 import numpy as np
 import pytest
 import torch

@@ -67,6 +67,12 @@ constexpr int WST = 136;           // LDS row stride of a staged weight chunk (W
 // the Hessian-label k_paths: 1 -> 4 r04o (same-box A/B, 2 pairs: 1.747 -> 1.719 ms/step)
 #define DPI_NOISE_UNROLL_HESS 4
 #endif
+#ifndef DPI_NOISE_TABLE_FO
+// the first-order Cha / OU k_paths and k_paths_fb instances (nx <= 128, no TD) take the wave-uniform
+// Philox words from a per-wave LDS table (dpi_rng.h NOISE_TABLE; paths_body); 0: the plain form (the
+// A/B knob, tools/build_variant.py)
+#define DPI_NOISE_TABLE_FO 1
+#endif
 constexpr int NXP_MAX = 128;       // max padded state dimension of the two-workgroups-per-CU path kernels
 // max state dimension of the wide first-order instances (Cha / OU, one workgroup per CU: the noise
 // tile of 256 dims x 64 paths is 70 KB of LDS; dpi_paths_wide_*.hip)
@@ -2285,7 +2291,31 @@ __device__ __forceinline__ void paths_body(const EqDev& e, const NET& net, const
   constexpr int NOISE_UNROLL = HESS ? DPI_NOISE_UNROLL_HESS
                                : GBM ? (ZERO ? 4 : DPI_NOISE_UNROLL_GBM)
                                      : DPI_NOISE_UNROLL_FO;
-  constexpr bool NOISE_WU = false;  // the plain philox4x32_10 (see wv below)
+  // The first-order Cha / OU instances (nx <= 128, no TD; the u = 0 twin too, so the noise-floor launch
+  // stays the same loop) read the wave-uniform Philox words from a per-wave table (dpi_rng.h
+  // NOISE_TABLE); everything else runs the plain philox4x32_10 (see wv below).
+  // The four tables (4 waves x 64 entries x 16 B = 4 KB) overlay the weight ring sh.W, which is idle
+  // during both rollouts — LdsT<128> leaves 1.5 KB per CU at two workgroups.  Two hazards:
+  //  - before the MLP: no wave's LDS-DMA (SplitStream::issue) or staged fp32 chunk may land in the
+  //    ring while another wave still reads its table.  Every phase order has a workgroup barrier
+  //    between its last rollout before the integrand and the integrand: the one after base_poll_
+  //    (terminal-last), terminal_finish's (terminal-first); the MLP's first write into the ring comes
+  //    after it.  The u = 0 instances never touch the ring.
+  //  - after the MLP (terminal-last order only): a wave that leaves the integrand builds its first
+  //    terminal table while a slower wave may still read the ring's last chunk.  So the tables are
+  //    the last 4 KB of the ring slot which that chunk does not occupy (ntab below).  Split MLP: chunk
+  //    idx sits in slot idx & 1, so the last of SplitStream's `total` chunks leaves slot total & 1;
+  //    the reads of the chunk before it, the free slot's last user, are retired by the barrier every
+  //    wave passed on entering the last chunk, and no LDS-DMA is issued past the last chunk.  Exact
+  //    fp32: every staged chunk is the ring's first 17 KB (32 rows of stride WST), slot 1's end is free.
+  //    No barrier is added (one between the integrand and the terminal rollout measured 2 us slower
+  //    per launch).
+  // One instance keeps the plain form: the split OU 4 x 128 ELU k_paths, at 255 registers without the
+  // table, spills 6 VGPRs at 256 with it (and its occupancy is not lowered to make it fit).
+  constexpr bool NOISE_TAB_SPILLS = KIND == DPI_EQ_OU && H == 128 && L == 4 && SPLIT && ACT == DPI_ACT_ELU;
+  constexpr bool NOISE_TAB =
+      DPI_NOISE_TABLE_FO && !GBM && !HESS && !TD && !GEN && NXW == NXP_MAX && !NOISE_TAB_SPILLS;
+  constexpr int NOISE_FORM = NOISE_TAB ? NOISE_TABLE : NOISE_PLAIN;
   // The wave index as the compiler sees it: divergent (tid >> 6), so the dim-block indices j and the
   // Philox counter words c0 = k nb + j live in VGPRs.  Made uniform (readfirstlane) with the
   // scalar-unit Philox (philox4x32_10_wu), the noise loop issues 195 instead of 216 VALU instructions
@@ -2294,6 +2324,15 @@ __device__ __forceinline__ void paths_body(const EqDev& e, const NET& net, const
   // k_noise_shared only.  DPI_WV_UNIFORM_GBM: the A/B knob for the GBM network launch.
   constexpr bool WV_UNIFORM = DPI_WV_UNIFORM_GBM && GBM && !HESS && !TD && NXW == NXP_MAX;
   const int tid = threadIdx.x, lane = tid & 63, wv = WV_UNIFORM ? __builtin_amdgcn_readfirstlane(tid >> 6) : tid >> 6;
+  [[maybe_unused]] u32e4* ntab = nullptr;  // this wave's Philox table (NOISE_TAB)
+  if constexpr (NOISE_TAB) {
+    constexpr int SLOT = 32 * HMAX, TAB = 4 * 64 * 4;  // floats: a ring slot, the four tables
+    static_assert(2 * SLOT * sizeof(float) == sizeof(sh.W) && 32 * WST <= 2 * SLOT - TAB,
+                  "the tables are the end of a ring slot, clear of a staged fp32 chunk");
+    int slot = 1;  // the slot the MLP's last chunk does not occupy (NOISE_TAB above)
+    if constexpr (SPLIT && !ZERO) slot = SplitStream<H, L, NXW>(net, Eq<KIND>::GRAD_FULL).total & 1;
+    ntab = reinterpret_cast<u32e4*>(sh.W + slot * SLOT + SLOT - TAB) + 64 * wv;
+  }
   const uint32_t ig = a.point_base + (uint32_t)i;
   const uint32_t m = (uint32_t)(a.m_begin + P * blk + lane);
   const int nx = e.nx, F = 1 + nx;
@@ -2436,7 +2475,7 @@ __device__ __forceinline__ void paths_body(const EqDev& e, const NET& net, const
           for (int q = 0; q < 4; ++q) ST[c][q] = np[(4 * j + q) * P];
         } else {
           float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-          noise_sums<NOISE_UNROLL, NOISE_WU>(a.K, nb, j, m, ig, a.c3t, a.k0, a.k1, s0, s1, s2, s3);
+          noise_sums<NOISE_UNROLL, NOISE_FORM>(a.K, nb, j, m, ig, a.c3t, a.k0, a.k1, s0, s1, s2, s3, ntab);
           ST[c][0] = s0 * BM_SCALE;
           ST[c][1] = s1 * BM_SCALE;
           ST[c][2] = s2 * BM_SCALE;
@@ -2457,7 +2496,7 @@ __device__ __forceinline__ void paths_body(const EqDev& e, const NET& net, const
       if (j < nb) {
         float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
         if (INTG && !PRE) {
-          noise_sums<NOISE_UNROLL, NOISE_WU>(a.K, nb, j, m, ig, a.c3i, a.k0, a.k1, s0, s1, s2, s3);
+          noise_sums<NOISE_UNROLL, NOISE_FORM>(a.K, nb, j, m, ig, a.c3i, a.k0, a.k1, s0, s1, s2, s3, ntab);
         }
         float sv[4] = {s0 * BM_SCALE, s1 * BM_SCALE, s2 * BM_SCALE, s3 * BM_SCALE};
         if (INTG && PRE) {  // rolled out by k_noise_shared (GBM prepared calls)

@@ -92,6 +92,76 @@ __device__ __forceinline__ u32x4 philox4x32_10_wu(uint32_t c0, uint32_t c1, uint
   return {c0, c1, c2, c3};
 }
 
+// The same words once more, with the wave-uniform work taken out of the call instead of moved to the
+// scalar unit.  In a rollout only c1 = m differs between lanes, so of a call's first three rounds
+//   round 1's M0 c0, round 2's M1 c2 and round 3's M0 c0                    are the same in all lanes,
+//   n0 = hi(M1 i) ^ m ^ k0 (round 1's c0) and q0 = M0 n0 (round 2's product)  never change in a kernel.
+// philox_table_entry() folds the uniform words and every round key that meets them into four words
+// E0..E3 per (k, j, i, c3, key); the lanes of a wave compute the entries of 64 steps k at once
+// (noise_sums, NOISE_TABLE).  philox_lane_invariant() is the per-lane part, philox4x32_10_tail() what
+// is left per call and lane: one product of round 3 and rounds 4..10, 15 v_mad_u64_u32 instead of 18.
+// Bitwise the words of philox4x32_10.  The three compile for the host too (tests/philox_table_host.hip;
+// v_bitop3 is a device builtin).
+#define DPI_HD __host__ __device__ __forceinline__
+typedef uint32_t u32e4 __attribute__((ext_vector_type(4)));  // a table entry (one ds_read_b128)
+DPI_HD uint32_t xor3(uint32_t a, uint32_t b, uint32_t c) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __builtin_amdgcn_bitop3_b32(a, b, c, 0x96);
+#else
+  return a ^ b ^ c;
+#endif
+}
+struct PhiloxLane {
+  uint32_t qh, ql;  // hi(q0), lo(q0)
+};
+DPI_HD PhiloxLane philox_lane_invariant(uint32_t m, uint32_t i, uint32_t k0) {
+  constexpr uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u;
+  const uint32_t n0 = xor3((uint32_t)(((uint64_t)M1 * i) >> 32), m, k0);
+  const uint64_t q0 = (uint64_t)M0 * n0;
+  return {(uint32_t)(q0 >> 32), (uint32_t)q0};
+}
+DPI_HD u32e4 philox_table_entry(uint32_t c0, uint32_t i, uint32_t c3, uint32_t k0, uint32_t k1) {
+  constexpr uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u, W0 = 0x9E3779B9u, W1 = 0xBB67AE85u;
+  const uint64_t p0 = (uint64_t)M0 * c0;
+  const uint32_t a = xor3((uint32_t)(p0 >> 32), c3, k1);  // round 1's c2
+  const uint32_t b = (uint32_t)p0;                        // round 1's c3
+  const uint64_t r1 = (uint64_t)M1 * a;
+  const uint32_t c = xor3((uint32_t)(r1 >> 32), M1 * i, k0 + W0);  // round 2's c0
+  const uint32_t d = (uint32_t)r1;                                 // round 2's c1
+  const uint64_t r0 = (uint64_t)M0 * c;
+  return u32e4{b ^ (k1 + W1), d ^ (k0 + 2 * W0), (uint32_t)(r0 >> 32) ^ (k1 + 2 * W1), (uint32_t)r0 ^ (k1 + 3 * W1)};
+}
+DPI_HD u32x4 philox4x32_10_tail(PhiloxLane li, u32e4 E, uint32_t k0, uint32_t k1) {
+  constexpr uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u, W0 = 0x9E3779B9u, W1 = 0xBB67AE85u;
+  // round 3's per-lane product; its other words come from the entry
+  const uint64_t q1 = (uint64_t)M1 * (li.qh ^ E[0]);
+  uint32_t c0 = (uint32_t)(q1 >> 32) ^ E[1], c1 = (uint32_t)q1, c2 = li.ql ^ E[2], c3;
+  k0 += 3 * W0, k1 += 4 * W1;
+  {  // round 4: round 3's c3 and the key k1 + 3 W1 are folded into E[3]
+    const uint64_t p0 = (uint64_t)M0 * c0;
+    const uint64_t p1 = (uint64_t)M1 * c2;
+    c0 = xor3((uint32_t)(p1 >> 32), c1, k0);
+    c2 = (uint32_t)(p0 >> 32) ^ E[3];
+    c1 = (uint32_t)p1;
+    c3 = (uint32_t)p0;
+    k0 += W0;
+  }
+#pragma unroll
+  for (int r = 4; r < 10; ++r) {
+    const uint64_t p0 = (uint64_t)M0 * c0;
+    const uint64_t p1 = (uint64_t)M1 * c2;
+    const uint32_t n0 = xor3((uint32_t)(p1 >> 32), c1, k0);
+    const uint32_t n2 = xor3((uint32_t)(p0 >> 32), c3, k1);
+    c1 = (uint32_t)p1;
+    c3 = (uint32_t)p0;
+    c0 = n0;
+    c2 = n2;
+    k0 += W0;
+    k1 += W1;
+  }
+  return {c0, c1, c2, c3};
+}
+
 // [0,1) and (0,1] from the top 24 bits: exact in fp32, identical to oracle/philox.py.
 __device__ __forceinline__ float u01_co(uint32_t w) { return (float)(w >> 8) * (1.0f / 16777216.0f); }
 __device__ __forceinline__ float u01_oc(uint32_t w) { return (float)((w >> 8) + 1u) * (1.0f / 16777216.0f); }
@@ -141,12 +211,54 @@ __device__ __forceinline__ f4 normals4(u32x4 w) {
 // counter word c0 = k nb + j), in k order.  philox4x32_10_wu's readfirstlane makes the loop body
 // convergent, which the compiler will not unroll by a runtime trip count: the loop is unrolled by
 // hand, UNR independent Philox chains per iteration and a remainder loop, summing in the same order.
-// WU = false: the plain philox4x32_10 (for kernels whose register budget the scalar form's extra live
-// values would overflow: the wide nx <= 256 instances, the GBM TD kernel, the shared PIS rollout wave).
-template <int UNR, bool WU = true>
+// FORM:
+//   NOISE_PLAIN  the plain philox4x32_10 under the compiler's own unroll (for kernels whose register
+//                budget the scalar form's extra live values would overflow: the wide nx <= 256
+//                instances, the GBM TD kernel, the shared PIS rollout wave);
+//   NOISE_WU     the scalar-unit form, philox4x32_10_wu (one wave per SIMD: k_noise_shared);
+//   NOISE_TABLE  the uniform words from a per-wave LDS table `tab` of 64 entries x 16 B, K in chunks of
+//                64 steps: lane l builds the entry of step kb + l, then the wave runs the chunk's steps
+//                in k order (UNR chains and a remainder loop, as above), each step fetching its entry
+//                with one ds_read_b128 at a wave-uniform address (a broadcast: no bank conflict, and
+//                no VALU or SALU instruction).  s0..s3 accumulate in the same k order across chunks,
+//                so the sums are bitwise those of the other forms.  The wave is the only writer and
+//                the only reader of its table and a wave's LDS operations complete in order, so a
+//                wavefront-scope fence and a wave barrier (no instruction: they keep the compiler
+//                from moving the build and the reads across each other) separate the two, and no
+//                workgroup barrier is needed.  Whoever else uses the table's memory is the caller's
+//                business (paths_body overlays it on the weight ring).
+enum NoiseForm { NOISE_PLAIN = 0, NOISE_WU = 1, NOISE_TABLE = 2 };
+__device__ __forceinline__ void wave_lds_order() {
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+}
+template <int UNR, int FORM = NOISE_WU>
 __device__ __forceinline__ void noise_sums(int K, int nb, int j, uint32_t m, uint32_t ig, uint32_t c3, uint32_t k0,
-                                           uint32_t k1, float& s0, float& s1, float& s2, float& s3) {
-  if constexpr (WU) {
+                                           uint32_t k1, float& s0, float& s1, float& s2, float& s3,
+                                           [[maybe_unused]] u32e4* tab = nullptr) {
+  if constexpr (FORM == NOISE_TABLE) {
+    const PhiloxLane li = philox_lane_invariant(m, ig, k0);
+    const uint32_t lane = threadIdx.x & 63u;
+    auto step = [&](u32e4 e) {
+      const f4 z = normals4_raw(philox4x32_10_tail(li, e, k0, k1));
+      s0 += z.a;
+      s1 += z.b;
+      s2 += z.c;
+      s3 += z.d;
+    };
+    for (int kb = 0; kb < K; kb += 64) {
+      wave_lds_order();  // the last chunk's reads are done
+      tab[lane] = philox_table_entry(((uint32_t)kb + lane) * (uint32_t)nb + (uint32_t)j, ig, c3, k0, k1);
+      wave_lds_order();
+      const int n = K - kb < 64 ? K - kb : 64;
+      int k = 0;
+      for (; k + UNR <= n; k += UNR) {
+#pragma unroll
+        for (int u = 0; u < UNR; ++u) step(tab[k + u]);
+      }
+      for (; k < n; ++k) step(tab[k]);
+    }
+  } else if constexpr (FORM == NOISE_WU) {
     auto step = [&](int k) {
       const f4 z = normals4_raw(philox4x32_10_wu((uint32_t)(k * nb + j), m, ig, c3, k0, k1));
       s0 += z.a;

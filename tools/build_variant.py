@@ -4,6 +4,7 @@ objects.  usage: python tools/build_variant.py NAME [--units U,..] -DX=Y ...
 -> tools/variants/libdpi_NAME.so (select it with DPI_HIP_LIB=...)."""
 import subprocess
 import sys
+from concurrent.futures import ThreadPoolExecutor
 from pathlib import Path
 
 ROOT = Path(__file__).resolve().parents[1]
@@ -17,11 +18,16 @@ if defs and defs[0] == "--units":
 B.build()
 out_dir = ROOT / "tools" / "variants"
 out_dir.mkdir(exist_ok=True)
-objs = []
-for u in units:
+
+
+def compile_unit(u):
     obj = out_dir / f"{Path(u).stem}_{name}.o"
     subprocess.run([B.HIPCC, *B.FLAGS, *defs, "-c", "-o", str(obj), str(B.CSRC / u)], check=True)
-    objs.append(obj)
+    return obj
+
+
+with ThreadPoolExecutor(max_workers=len(units)) as ex:  # the units in parallel, as build.py compiles them
+    objs = list(ex.map(compile_unit, units))
 objs += [B.OBJ / (Path(u).stem + ".o") for u in B.UNITS if u not in units] + [B.OBJ / "dpi_build_id.o"]
 so = out_dir / f"libdpi_{name}.so"
 subprocess.run([B.HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", str(so), *map(str, objs)], check=True)

@@ -10,5 +10,5 @@ __version__ = "0.1.0"
 
 from . import _lib  # noqa: F401
 from .equations import Cha, GBMEquationComplexExact, OUProcessEquation  # noqa: F401
-from .solution import DeviceNet, PISGradNet, ZeroSolution, construct_mlp  # noqa: F401
+from .solution import DeviceNet, PicardSolutionEnforceTerminal, PISGradNet, ZeroSolution, construct_mlp  # noqa: F401
 from .data import OnlineDataGenerator  # noqa: F401

@@ -45,6 +45,8 @@ SIGNATURES = {
     "dpi_net_create_zero": (c_int, [P(c_void_p)]),
     "dpi_net_create_mlp": (c_int, [c_int, c_int, P(c_int), c_int, P(c_float), c_size_t, P(c_void_p)]),
     "dpi_net_create_mlp_head": (c_int, [c_int, c_int, P(c_int), c_int, c_int, P(c_float), c_size_t, P(c_void_p)]),
+    "dpi_net_create_mlp_terminal": (c_int, [c_int, c_int, P(c_int), c_int, c_int, c_double, P(c_float), c_size_t,
+                                            P(c_void_p)]),
     "dpi_net_create_pisgrad": (c_int, [c_int, c_int, P(c_int), c_double, P(c_float), c_size_t, P(c_void_p)]),
     "dpi_net_destroy": (c_int, [c_void_p]),
     "dpi_pair_family": (c_int, [c_void_p, c_void_p, c_int, P(c_int)]),

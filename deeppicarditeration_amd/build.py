@@ -27,7 +27,12 @@ UNITS = ["dpi_kernels.hip", "dpi_paths_cha.hip", "dpi_paths_ou.hip", "dpi_paths_
          "dpi_paths_gen_ou_tanh.hip", "dpi_paths_head_cha_128.hip", "dpi_paths_head_cha_256.hip",
          "dpi_paths_head_ou_128.hip", "dpi_paths_head_ou_256.hip", "dpi_paths_head_cha_128_tanh.hip",
          "dpi_paths_head_cha_256_tanh.hip", "dpi_paths_head_ou_128_tanh.hip", "dpi_paths_head_ou_256_tanh.hip",
-         "dpi_paths_head_base_cha.hip", "dpi_paths_head_base_ou.hip"]
+         "dpi_paths_head_base_cha.hip", "dpi_paths_head_base_ou.hip", "dpi_paths_term_cha.hip", "dpi_paths_term_ou.hip",
+         "dpi_paths_term_cha_tanh.hip", "dpi_paths_term_ou_tanh.hip", "dpi_paths_term_head_cha_128.hip",
+         "dpi_paths_term_head_cha_256.hip", "dpi_paths_term_head_ou_128.hip", "dpi_paths_term_head_ou_256.hip",
+         "dpi_paths_term_head_cha_128_tanh.hip", "dpi_paths_term_head_cha_256_tanh.hip",
+         "dpi_paths_term_head_ou_128_tanh.hip", "dpi_paths_term_head_ou_256_tanh.hip",
+         "dpi_paths_term_head_base_cha.hip", "dpi_paths_term_head_base_ou.hip"]
 OBJ = ROOT / "build"
 OUT = ROOT / "libdpi_hip.so"
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

@@ -2250,12 +2250,15 @@ constexpr int k_paths_wgs() {
 // layer count is read at run time): phase 2 is mlp_tile_gen, gbid is the block index within the call
 // (the launch's first block + blockIdx.x) and stash the workgroup's stash slot.  NET = NetGenHead: its
 // direct-gradient head form (k_paths_head): one launch over all blocks, no stash.
+// TERMA (general family only): the net is read as the terminal-enforcing ansatz (dpi_general.h), which
+// needs T - s of every path: (T - t)(1 - U), parked in sh.bsh until the integrand overwrites it.
 template <int KIND, int H, int L, bool ZERO, bool SPLIT, bool HESS, bool TD, int ACT, bool FBT, int NXW = NXP_MAX,
-          class NET = NetDev>
+          class NET = NetDev, bool TERMA = false>
 __device__ __forceinline__ void paths_body(const EqDev& e, const NET& net, const PathArgs& a, const FusedBase& fb,
                                            unsigned gbid = 0u, floatx4* stash = nullptr) {
   constexpr bool HEAD = std::is_same_v<NET, NetGenHead>;
   constexpr bool GEN = std::is_same_v<NET, NetGen> || HEAD;
+  static_assert(!TERMA || GEN, "the terminal ansatz: general-family nets");
   static_assert(!GEN || (KIND != DPI_EQ_GBM && !ZERO && !SPLIT && !HESS && !TD && !FBT && NXW == NXP_MAX),
                 "the general family: first-order Cha / OU labels, exact fp32, nx <= 128");
   static_assert(!HESS || KIND == DPI_EQ_GBM, "Hessian labels: GBM (SimpleDiffusionEquationWithHessian) only");
@@ -2436,6 +2439,7 @@ __device__ __forceinline__ void paths_body(const EqDev& e, const NET& net, const
   if (wv == 0) {
     sh.tau[lane] = s;
     sh.cmul[lane] = cI;
+    if constexpr (TERMA) sh.bsh[lane] = tmt * (1.0f - U);  // T - s, without the cancellation of T - fl(s)
   }
   __syncthreads();  // xsh ready
 
@@ -2545,7 +2549,7 @@ __device__ __forceinline__ void paths_body(const EqDev& e, const NET& net, const
       float u = 0.f, gs = 0.f, gA = 0.f, gB = 0.f;
       if (!ZERO && INTG) {
         if constexpr (GEN)
-          mlp_tile_gen<KIND, H, ACT>(e, net, sh, stash, u, gs, gA, gB);
+          mlp_tile_gen<KIND, H, ACT, NET, TERMA>(e, net, sh, stash, u, gs, gA, gB);
         else if constexpr (SPLIT)
           mlp_tile_split<KIND, H, L, ACT>(e, net, sh, u, gs, gA, gB);
         else
@@ -2855,6 +2859,19 @@ template <int KIND, int HCAP, int ACT>
 __global__ __launch_bounds__(256, (gen_wgs(HCAP))) void k_paths_head(EqDev e, NetGenHead net, PathArgs a) {
   paths_body<KIND, HCAP, GEN_LMAX, false, false, false, false, ACT, false, NXP_MAX, NetGenHead>(e, net, a, FusedBase{},
                                                                                                  blockIdx.x, nullptr);
+}
+// The terminal-enforcing forms of both (dpi_general.h, TERMA): launched as their plain twins are.
+template <int KIND, int HCAP, int ACT>
+__global__ __launch_bounds__(256, (gen_wgs(HCAP))) void k_paths_term(EqDev e, NetGen net, PathArgs a, floatx4* stash,
+                                                                   unsigned block0) {
+  floatx4* const slot = stash + (size_t)blockIdx.x * (gen_slot_floats(net.L, net.ht) / 4);
+  paths_body<KIND, HCAP, GEN_LMAX, false, false, false, false, ACT, false, NXP_MAX, NetGen, true>(
+      e, net, a, FusedBase{}, block0 + blockIdx.x, slot);
+}
+template <int KIND, int HCAP, int ACT>
+__global__ __launch_bounds__(256, (gen_wgs(HCAP))) void k_paths_head_term(EqDev e, NetGenHead net, PathArgs a) {
+  paths_body<KIND, HCAP, GEN_LMAX, false, false, false, false, ACT, false, NXP_MAX, NetGenHead, true>(
+      e, net, a, FusedBase{}, blockIdx.x, nullptr);
 }
 
 }  // namespace dpi

@@ -28,6 +28,10 @@ struct dpi_net_s {
   // NetGen part); head: DPI_HEAD_*
   NetGenHead hd{};
   int head = 0;
+  // terminal-enforcing nets (dpi_net_create_mlp_terminal): the general image only, g (a value net) or hd
+  // (an OnlyGradient head), read as the ansatz around g; term_T: the T it was built for
+  bool term = false;
+  float term_T = 0.f;
   void* blob = nullptr;
   int n_in = 0;
   int precision = -1;     // DPI_GEMM_* for this net (dpi_net_set_precision); -1: the process-wide mode
@@ -61,6 +65,7 @@ struct Launch {
   bool gen = false;         // the pair runs the general MLP family (dpi_kernels.hip pair_route)
   floatx4* stash = nullptr;  // its stash region of the workspace (path launches)
   bool head = false;        // ... in its head form (a ValueGradient / OnlyGradient net): no stash
+  bool term = false;        // ... read as the terminal-enforcing ansatz
 };
 // The path launches (k_paths, k_paths_fb) of a Launch, with its timer events when armed.
 #define DPI_PATH_LAUNCH(KERN, q, ...) \
@@ -147,13 +152,18 @@ constexpr bool spec_shape(int kind, int H, int L) {
 
 // The general MLP family's units (GENV rows of DPI_UNITS): k_paths_gen at both width caps, and — in
 // the ELU units, like k_baseline — the activation-generic k_baseline_gen.
-template <int KIND, int ACT>
+// TERMV: the terminal-enforcing twins (k_paths_term, k_baseline_term), in units of their own.
+template <int KIND, int ACT, bool TERMV = false>
 bool dispatch_gen(const dpi_problem_s* p, const dpi_net_s* net, const Launch& q) {
   const NetGen& g = net->g;
   if (q.baseline) {
     if constexpr (ACT == DPI_ACT_ELU) {
-      hipLaunchKernelGGL((k_baseline_gen<KIND>), dim3(q.n), dim3(NTB), 0, q.st, p->e, g, q.tx, q.n, q.gx, q.fb, q.bx,
-                         q.smp, q.tickets);
+      if constexpr (TERMV)
+        hipLaunchKernelGGL((k_baseline_term<KIND>), dim3(q.n), dim3(NTB), 0, q.st, p->e, g, q.tx, q.n, q.gx, q.fb,
+                           q.bx, q.smp, q.tickets);
+      else
+        hipLaunchKernelGGL((k_baseline_gen<KIND>), dim3(q.n), dim3(NTB), 0, q.st, p->e, g, q.tx, q.n, q.gx, q.fb,
+                           q.bx, q.smp, q.tickets);
       return true;
     }
     return false;
@@ -165,7 +175,14 @@ bool dispatch_gen(const dpi_problem_s* p, const dpi_net_s* net, const Launch& q)
   for (unsigned b0 = 0; b0 < nblocks; b0 += slots) {
     const unsigned grid = std::min(nblocks - b0, slots);
     hipEvent_t t0 = b0 ? nullptr : q.t0, t1 = b0 ? nullptr : q.t1;
-    if (g.H == 128)
+    if constexpr (TERMV) {
+      if (g.H == 128)
+        hipExtLaunchKernelGGL((k_paths_term<KIND, 128, ACT>), dim3(grid), dim3(NTH), 0, q.st, t0, t1, 0, p->e, g, *q.a,
+                              q.stash, b0);
+      else
+        hipExtLaunchKernelGGL((k_paths_term<KIND, 256, ACT>), dim3(grid), dim3(NTH), 0, q.st, t0, t1, 0, p->e, g, *q.a,
+                              q.stash, b0);
+    } else if (g.H == 128)
       hipExtLaunchKernelGGL((k_paths_gen<KIND, 128, ACT>), dim3(grid), dim3(NTH), 0, q.st, t0, t1, 0, p->e, g, *q.a,
                             q.stash, b0);
     else
@@ -179,32 +196,39 @@ bool dispatch_gen(const dpi_problem_s* p, const dpi_net_s* net, const Launch& q)
 // k_paths_head at that width cap, one launch over all blocks; HEADV = HEAD_BASE the activation-generic
 // k_baseline_head.
 constexpr int HEAD_BASE = 1;
-template <int KIND, int ACT, int HEADV>
+template <int KIND, int ACT, int HEADV, bool TERMV = false>
 bool dispatch_head(const dpi_problem_s* p, const dpi_net_s* net, const Launch& q) {
   const NetGenHead& g = net->hd;
   if constexpr (HEADV == HEAD_BASE) {
     if (!q.baseline) return false;
-    hipLaunchKernelGGL((k_baseline_head<KIND>), dim3(q.n), dim3(NTB), 0, q.st, p->e, g, q.tx, q.n, q.gx, q.fb, q.bx,
-                       q.smp, q.tickets);
+    if constexpr (TERMV)
+      hipLaunchKernelGGL((k_baseline_head_term<KIND>), dim3(q.n), dim3(NTB), 0, q.st, p->e, g, q.tx, q.n, q.gx, q.fb,
+                         q.bx, q.smp, q.tickets);
+    else
+      hipLaunchKernelGGL((k_baseline_head<KIND>), dim3(q.n), dim3(NTB), 0, q.st, p->e, g, q.tx, q.n, q.gx, q.fb, q.bx,
+                         q.smp, q.tickets);
     return true;
   } else {
     if (q.baseline || q.hess || q.td || q.fbase || g.H != HEADV) return false;
-    DPI_PATH_LAUNCH((k_paths_head<KIND, HEADV, ACT>), q, p->e, g, *q.a);
+    if constexpr (TERMV)
+      DPI_PATH_LAUNCH((k_paths_head_term<KIND, HEADV, ACT>), q, p->e, g, *q.a);
+    else
+      DPI_PATH_LAUNCH((k_paths_head<KIND, HEADV, ACT>), q, p->e, g, *q.a);
     return true;
   }
 }
 
 template <int KIND, bool TDV = false, int ACT = DPI_ACT_ELU, bool FBV = false, int NXW = NXP_MAX, bool GENV = false,
-          int HEADV = 0>
+          int HEADV = 0, bool TERMV = false>
 bool dpi_dispatch(const dpi_problem_s* p, const dpi_net_s* net, const Launch& q) {
   if constexpr (GENV) {
     static_assert(KIND != DPI_EQ_GBM && !TDV && !FBV && NXW == NXP_MAX, "the general family: first-order Cha / OU");
     if constexpr (HEADV != 0)
-      return dispatch_head<KIND, ACT, HEADV>(p, net, q);
+      return dispatch_head<KIND, ACT, HEADV, TERMV>(p, net, q);
     else
-      return dispatch_gen<KIND, ACT>(p, net, q);
+      return dispatch_gen<KIND, ACT, TERMV>(p, net, q);
   } else {
-  static_assert(HEADV == 0, "head units are general-family units");
+  static_assert(HEADV == 0 && !TERMV, "head and terminal-enforcing units are general-family units");
   if constexpr (NXW > NXP_MAX) {
     if (q.baseline || q.hess || q.fbase) return false;
   }
@@ -241,45 +265,59 @@ bool dpi_dispatch(const dpi_problem_s* p, const dpi_net_s* net, const Launch& q)
 }
 
 // ---- the unit table: one row per dpi_paths_*.hip translation unit, keyed by dpi_dispatch's template
-// arguments (KIND, TDV, ACT, FBV, NXW, GENV, HEADV).  Each unit file holds the explicit instantiation of its row
+// arguments (KIND, TDV, ACT, FBV, NXW, GENV, HEADV, TERMV).  Each unit file holds the explicit instantiation of its row
 // (DPI_UNIT_DEFINE) and nothing else; every other unit sees the row as an extern template, so a row
 // without a unit fails at link time.  dpi_kernels.hip dispatch_any derives the key of a launch and
 // looks it up here.
 #define DPI_UNITS(X)                                                \
-  X(cha, DPI_EQ_CHA, false, DPI_ACT_ELU, false, NXP_MAX, false, 0)            \
-  X(ou, DPI_EQ_OU, false, DPI_ACT_ELU, false, NXP_MAX, false, 0)              \
-  X(gbm, DPI_EQ_GBM, false, DPI_ACT_ELU, false, NXP_MAX, false, 0)            \
-  X(td_cha, DPI_EQ_CHA, true, DPI_ACT_ELU, false, NXP_MAX, false, 0)          \
-  X(td_ou, DPI_EQ_OU, true, DPI_ACT_ELU, false, NXP_MAX, false, 0)            \
-  X(td_gbm, DPI_EQ_GBM, true, DPI_ACT_ELU, false, NXP_MAX, false, 0)          \
-  X(cha_tanh, DPI_EQ_CHA, false, DPI_ACT_TANH, false, NXP_MAX, false, 0)      \
-  X(ou_tanh, DPI_EQ_OU, false, DPI_ACT_TANH, false, NXP_MAX, false, 0)        \
-  X(gbm_tanh, DPI_EQ_GBM, false, DPI_ACT_TANH, false, NXP_MAX, false, 0)      \
-  X(td_cha_tanh, DPI_EQ_CHA, true, DPI_ACT_TANH, false, NXP_MAX, false, 0)    \
-  X(td_ou_tanh, DPI_EQ_OU, true, DPI_ACT_TANH, false, NXP_MAX, false, 0)      \
-  X(td_gbm_tanh, DPI_EQ_GBM, true, DPI_ACT_TANH, false, NXP_MAX, false, 0)    \
-  X(fb_cha, DPI_EQ_CHA, false, DPI_ACT_ELU, true, NXP_MAX, false, 0)          \
-  X(fb_ou, DPI_EQ_OU, false, DPI_ACT_ELU, true, NXP_MAX, false, 0)            \
-  X(wide_cha, DPI_EQ_CHA, false, DPI_ACT_ELU, false, NXW_MAX, false, 0)       \
-  X(wide_ou, DPI_EQ_OU, false, DPI_ACT_ELU, false, NXW_MAX, false, 0)         \
-  X(wide_gbm, DPI_EQ_GBM, false, DPI_ACT_ELU, false, NXW_MAX, false, 0)       \
-  X(wide_cha_tanh, DPI_EQ_CHA, false, DPI_ACT_TANH, false, NXW_MAX, false, 0) \
-  X(wide_ou_tanh, DPI_EQ_OU, false, DPI_ACT_TANH, false, NXW_MAX, false, 0)   \
-  X(wide_gbm_tanh, DPI_EQ_GBM, false, DPI_ACT_TANH, false, NXW_MAX, false, 0) \
-  X(gen_cha, DPI_EQ_CHA, false, DPI_ACT_ELU, false, NXP_MAX, true, 0) \
-  X(gen_ou, DPI_EQ_OU, false, DPI_ACT_ELU, false, NXP_MAX, true, 0) \
-  X(gen_cha_tanh, DPI_EQ_CHA, false, DPI_ACT_TANH, false, NXP_MAX, true, 0) \
-  X(gen_ou_tanh, DPI_EQ_OU, false, DPI_ACT_TANH, false, NXP_MAX, true, 0) \
-  X(head_cha_128, DPI_EQ_CHA, false, DPI_ACT_ELU, false, NXP_MAX, true, 128) \
-  X(head_cha_256, DPI_EQ_CHA, false, DPI_ACT_ELU, false, NXP_MAX, true, 256) \
-  X(head_ou_128, DPI_EQ_OU, false, DPI_ACT_ELU, false, NXP_MAX, true, 128) \
-  X(head_ou_256, DPI_EQ_OU, false, DPI_ACT_ELU, false, NXP_MAX, true, 256) \
-  X(head_cha_128_tanh, DPI_EQ_CHA, false, DPI_ACT_TANH, false, NXP_MAX, true, 128) \
-  X(head_cha_256_tanh, DPI_EQ_CHA, false, DPI_ACT_TANH, false, NXP_MAX, true, 256) \
-  X(head_ou_128_tanh, DPI_EQ_OU, false, DPI_ACT_TANH, false, NXP_MAX, true, 128) \
-  X(head_ou_256_tanh, DPI_EQ_OU, false, DPI_ACT_TANH, false, NXP_MAX, true, 256) \
-  X(head_base_cha, DPI_EQ_CHA, false, DPI_ACT_ELU, false, NXP_MAX, true, HEAD_BASE) \
-  X(head_base_ou, DPI_EQ_OU, false, DPI_ACT_ELU, false, NXP_MAX, true, HEAD_BASE)
+  X(cha, DPI_EQ_CHA, false, DPI_ACT_ELU, false, NXP_MAX, false, 0, false)            \
+  X(ou, DPI_EQ_OU, false, DPI_ACT_ELU, false, NXP_MAX, false, 0, false)              \
+  X(gbm, DPI_EQ_GBM, false, DPI_ACT_ELU, false, NXP_MAX, false, 0, false)            \
+  X(td_cha, DPI_EQ_CHA, true, DPI_ACT_ELU, false, NXP_MAX, false, 0, false)          \
+  X(td_ou, DPI_EQ_OU, true, DPI_ACT_ELU, false, NXP_MAX, false, 0, false)            \
+  X(td_gbm, DPI_EQ_GBM, true, DPI_ACT_ELU, false, NXP_MAX, false, 0, false)          \
+  X(cha_tanh, DPI_EQ_CHA, false, DPI_ACT_TANH, false, NXP_MAX, false, 0, false)      \
+  X(ou_tanh, DPI_EQ_OU, false, DPI_ACT_TANH, false, NXP_MAX, false, 0, false)        \
+  X(gbm_tanh, DPI_EQ_GBM, false, DPI_ACT_TANH, false, NXP_MAX, false, 0, false)      \
+  X(td_cha_tanh, DPI_EQ_CHA, true, DPI_ACT_TANH, false, NXP_MAX, false, 0, false)    \
+  X(td_ou_tanh, DPI_EQ_OU, true, DPI_ACT_TANH, false, NXP_MAX, false, 0, false)      \
+  X(td_gbm_tanh, DPI_EQ_GBM, true, DPI_ACT_TANH, false, NXP_MAX, false, 0, false)    \
+  X(fb_cha, DPI_EQ_CHA, false, DPI_ACT_ELU, true, NXP_MAX, false, 0, false)          \
+  X(fb_ou, DPI_EQ_OU, false, DPI_ACT_ELU, true, NXP_MAX, false, 0, false)            \
+  X(wide_cha, DPI_EQ_CHA, false, DPI_ACT_ELU, false, NXW_MAX, false, 0, false)       \
+  X(wide_ou, DPI_EQ_OU, false, DPI_ACT_ELU, false, NXW_MAX, false, 0, false)         \
+  X(wide_gbm, DPI_EQ_GBM, false, DPI_ACT_ELU, false, NXW_MAX, false, 0, false)       \
+  X(wide_cha_tanh, DPI_EQ_CHA, false, DPI_ACT_TANH, false, NXW_MAX, false, 0, false) \
+  X(wide_ou_tanh, DPI_EQ_OU, false, DPI_ACT_TANH, false, NXW_MAX, false, 0, false)   \
+  X(wide_gbm_tanh, DPI_EQ_GBM, false, DPI_ACT_TANH, false, NXW_MAX, false, 0, false) \
+  X(gen_cha, DPI_EQ_CHA, false, DPI_ACT_ELU, false, NXP_MAX, true, 0, false) \
+  X(gen_ou, DPI_EQ_OU, false, DPI_ACT_ELU, false, NXP_MAX, true, 0, false) \
+  X(gen_cha_tanh, DPI_EQ_CHA, false, DPI_ACT_TANH, false, NXP_MAX, true, 0, false) \
+  X(gen_ou_tanh, DPI_EQ_OU, false, DPI_ACT_TANH, false, NXP_MAX, true, 0, false) \
+  X(head_cha_128, DPI_EQ_CHA, false, DPI_ACT_ELU, false, NXP_MAX, true, 128, false) \
+  X(head_cha_256, DPI_EQ_CHA, false, DPI_ACT_ELU, false, NXP_MAX, true, 256, false) \
+  X(head_ou_128, DPI_EQ_OU, false, DPI_ACT_ELU, false, NXP_MAX, true, 128, false) \
+  X(head_ou_256, DPI_EQ_OU, false, DPI_ACT_ELU, false, NXP_MAX, true, 256, false) \
+  X(head_cha_128_tanh, DPI_EQ_CHA, false, DPI_ACT_TANH, false, NXP_MAX, true, 128, false) \
+  X(head_cha_256_tanh, DPI_EQ_CHA, false, DPI_ACT_TANH, false, NXP_MAX, true, 256, false) \
+  X(head_ou_128_tanh, DPI_EQ_OU, false, DPI_ACT_TANH, false, NXP_MAX, true, 128, false) \
+  X(head_ou_256_tanh, DPI_EQ_OU, false, DPI_ACT_TANH, false, NXP_MAX, true, 256, false) \
+  X(head_base_cha, DPI_EQ_CHA, false, DPI_ACT_ELU, false, NXP_MAX, true, HEAD_BASE, false) \
+  X(head_base_ou, DPI_EQ_OU, false, DPI_ACT_ELU, false, NXP_MAX, true, HEAD_BASE, false) \
+  X(term_cha, DPI_EQ_CHA, false, DPI_ACT_ELU, false, NXP_MAX, true, 0, true) \
+  X(term_ou, DPI_EQ_OU, false, DPI_ACT_ELU, false, NXP_MAX, true, 0, true) \
+  X(term_cha_tanh, DPI_EQ_CHA, false, DPI_ACT_TANH, false, NXP_MAX, true, 0, true) \
+  X(term_ou_tanh, DPI_EQ_OU, false, DPI_ACT_TANH, false, NXP_MAX, true, 0, true) \
+  X(term_head_cha_128, DPI_EQ_CHA, false, DPI_ACT_ELU, false, NXP_MAX, true, 128, true) \
+  X(term_head_cha_256, DPI_EQ_CHA, false, DPI_ACT_ELU, false, NXP_MAX, true, 256, true) \
+  X(term_head_ou_128, DPI_EQ_OU, false, DPI_ACT_ELU, false, NXP_MAX, true, 128, true) \
+  X(term_head_ou_256, DPI_EQ_OU, false, DPI_ACT_ELU, false, NXP_MAX, true, 256, true) \
+  X(term_head_cha_128_tanh, DPI_EQ_CHA, false, DPI_ACT_TANH, false, NXP_MAX, true, 128, true) \
+  X(term_head_cha_256_tanh, DPI_EQ_CHA, false, DPI_ACT_TANH, false, NXP_MAX, true, 256, true) \
+  X(term_head_ou_128_tanh, DPI_EQ_OU, false, DPI_ACT_TANH, false, NXP_MAX, true, 128, true) \
+  X(term_head_ou_256_tanh, DPI_EQ_OU, false, DPI_ACT_TANH, false, NXP_MAX, true, 256, true) \
+  X(term_head_base_cha, DPI_EQ_CHA, false, DPI_ACT_ELU, false, NXP_MAX, true, HEAD_BASE, true) \
+  X(term_head_base_ou, DPI_EQ_OU, false, DPI_ACT_ELU, false, NXP_MAX, true, HEAD_BASE, true)
 
 struct Unit {
   int kind;
@@ -289,9 +327,10 @@ struct Unit {
   int nxw;
   bool gen;
   int head;  // 0, or a head unit's HEADV
+  bool term;  // the terminal-enforcing twin of a general-family unit
   bool (*dispatch)(const dpi_problem_s*, const dpi_net_s*, const Launch&);
-  constexpr bool is(int k, bool t, int a, bool f, int w, bool g = false, int h = 0) const {
-    return kind == k && td == t && act == a && fb == f && nxw == w && gen == g && head == h;
+  constexpr bool is(int k, bool t, int a, bool f, int w, bool g = false, int h = 0, bool tm = false) const {
+    return kind == k && td == t && act == a && fb == f && nxw == w && gen == g && head == h && term == tm;
   }
 };
 #define DPI_UNIT_EXTERN(NAME, ...) \
@@ -308,15 +347,16 @@ constexpr Unit UNITS[N_UNITS] = {DPI_UNITS(DPI_UNIT_ROW)};
 constexpr bool units_distinct() {
   for (int i = 0; i < N_UNITS; ++i)
     for (int j = 0; j < i; ++j)
-      if (UNITS[i].is(UNITS[j].kind, UNITS[j].td, UNITS[j].act, UNITS[j].fb, UNITS[j].nxw, UNITS[j].gen, UNITS[j].head))
+      if (UNITS[i].is(UNITS[j].kind, UNITS[j].td, UNITS[j].act, UNITS[j].fb, UNITS[j].nxw, UNITS[j].gen, UNITS[j].head,
+                      UNITS[j].term))
         return false;
   return true;
 }
-static_assert(units_distinct(), "two rows of DPI_UNITS share a (KIND, TDV, ACT, FBV, NXW, GENV, HEADV) key");
+static_assert(units_distinct(), "two rows of DPI_UNITS share a (KIND, TDV, ACT, FBV, NXW, GENV, HEADV, TERMV) key");
 
 // The whole of dpi_paths_<NAME>.hip: the row's template arguments are written in DPI_UNITS only.
 #define DPI_UNIT_DEFINE(NAME)                                                                                   \
   template bool dpi_dispatch<UNITS[UNIT_##NAME].kind, UNITS[UNIT_##NAME].td, UNITS[UNIT_##NAME].act,            \
                              UNITS[UNIT_##NAME].fb, UNITS[UNIT_##NAME].nxw, UNITS[UNIT_##NAME].gen,                \
-                             UNITS[UNIT_##NAME].head>(                                                          \
+                             UNITS[UNIT_##NAME].head, UNITS[UNIT_##NAME].term>(                                 \
       const dpi_problem_s*, const dpi_net_s*, const Launch&);

@@ -89,6 +89,39 @@ struct Eq<DPI_EQ_OU> {
       if (c < e.ncomp) s += __expf(lp[c] - mx);
     return -(mx + __logf(s));
   }
+  // gstat / gfin for the terminal-enforcing ansatz (dpi_general.h), which also needs the responsibilities
+  // r_c = softmax_c(logc_c - st_c / 2): grad_d g = sum_c r_c (X_d - mean_cd) ivar_cd.  The exponents are
+  // near -2.8 nx, where one fp32 ulp is 3e-5 at nx = 100, and unlike g, which takes their logarithm, r_c
+  // exponentiates their differences: the statistics are summed and the differences formed in fp64, and
+  // only lp_c - max is rounded to fp32.  gstat / gfin above stay as they are (every other kernel's).
+  __device__ static __forceinline__ void gstat_d(const EqDev& e, int d, float X, double* st) {
+#pragma unroll
+    for (int c = 0; c < NSG; ++c) {
+      if (c < e.ncomp) {
+        const double df = (double)X - (double)e.mean[c * e.nx + d];
+        st[c] = fma(df * df, (double)e.ivar[c * e.nx + d], st[c]);
+      }
+    }
+  }
+  __device__ static __forceinline__ float gfin_w(const EqDev& e, const double* st, float* rc) {
+    double lp[NSG];
+    double mx = -1.0e300;
+#pragma unroll
+    for (int c = 0; c < NSG; ++c) {
+      lp[c] = (c < e.ncomp) ? (double)e.logc[c] - 0.5 * st[c] : -1.0e300;
+      mx = fmax(mx, lp[c]);
+    }
+    float s = 0.f;
+#pragma unroll
+    for (int c = 0; c < NSG; ++c) {
+      rc[c] = (c < e.ncomp) ? __expf((float)(lp[c] - mx)) : 0.f;
+      s += rc[c];
+    }
+    const float is = 1.0f / s;
+#pragma unroll
+    for (int c = 0; c < NSG; ++c) rc[c] *= is;
+    return (float)-(mx + (double)__logf(s));
+  }
   __device__ static __forceinline__ void gacc(const EqDev& e, int d, float X, float z, float& A, float& B) {
     A = fmaf(X - e.ou_mu, z, A);
     B = fmaf(z, z, B);

@@ -19,6 +19,13 @@
 // all its blocks.  The gradient block G (nx x H_last) of the last Linear is laid out as W1xT is, one
 // row per state dimension, and feeds the same gen_stage + gen_dot loop with a_L as the B operand; Cha,
 // which needs only sum_d u_x[d], takes it from cg = sum_d G[d] instead (two dots, no output GEMM).
+//
+// Terminal-enforcing nets (TERMA = true; the reference's PicardSolutionEnforceTerminal): the same two
+// images, read as the hard-constraint ansatz u = g + (T - s) N (a value net) or
+// grad u = grad g + (T - s) (G a_L + bg), u = 0 (an OnlyGradient head).  After the network phase every
+// path takes g(X_s) and grad g(X_s) from one pass over its state dimensions (term_g); kernels of their
+// own (k_paths_term, k_paths_head_term, k_baseline_term, k_baseline_head_term), so the existing ones
+// keep their registers.
 #pragma once
 
 namespace dpi {
@@ -109,11 +116,57 @@ __device__ __forceinline__ floatx4 gen_dot(const float* wrow, const float (&b)[H
   return acc;
 }
 
+// Sums of fp64 statistics over the 4 lane groups of the MFMA C layout (as qsum) and over a wave.
+__device__ __forceinline__ double qsum_d(double v) {
+  v += __shfl_xor(v, 32, 64);
+  return v + __shfl_xor(v, 16, 64);
+}
+__device__ __forceinline__ double wave_sum_d(double v) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+// The terminal ansatz's g at X_s[d] = xsh[d] + cm S[d][pp] of path pp: the four lane groups split the
+// dimensions (d = qq, qq + 4, ...) and are joined as qsum joins them.  Cha: returns g; grad_d g =
+// k' g (1 - g) for every d.  OU: returns g = -log p_GMM and leaves the responsibilities r_c in rc
+// (Eq<OU>::gstat_d / gfin_w: fp64 statistics); grad_d g = sum_c r_c (X_d - mean_cd) ivar_cd (term_dg).
+// Reached by every lane of the workgroup: the loop bounds differ per lane group, the joins do not.
+template <int KIND, int HCAP>
+__device__ __forceinline__ float term_g(const EqDev& e, const LdsGen<HCAP>& sh, int pp, int qq, float cm,
+                                        float (&rc)[NSG]) {
+  if constexpr (!Eq<KIND>::GRAD_FULL) {
+    float st[NSG];  // Cha: sum_d X_d in st[0]
+#pragma unroll
+    for (int c = 0; c < NSG; ++c) st[c] = rc[c] = 0.f;
+    for (int d = qq; d < e.nx; d += 4) Eq<KIND>::gstat(e, d, fmaf(cm, sh.S[d * SS + pp], sh.xsh[d]), st);
+    st[0] = qsum(st[0]);
+    return Eq<KIND>::gfin(e, st);
+  } else {
+    double st[NSG];
+#pragma unroll
+    for (int c = 0; c < NSG; ++c) st[c] = 0.0;
+    for (int d = qq; d < e.nx; d += 4) Eq<KIND>::gstat_d(e, d, fmaf(cm, sh.S[d * SS + pp], sh.xsh[d]), st);
+#pragma unroll
+    for (int c = 0; c < NSG; ++c) st[c] = qsum_d(st[c]);
+    return Eq<KIND>::gfin_w(e, st, rc);
+  }
+}
+// grad_d g of the OU mixture at X (the state's dimension d) from the responsibilities
+__device__ __forceinline__ float term_dg(const EqDev& e, int d, float X, const float (&rc)[NSG]) {
+  float z = 0.f;
+#pragma unroll
+  for (int c = 0; c < NSG; ++c)
+    if (c < e.ncomp) z = fmaf(rc[c] * (X - e.mean[c * e.nx + d]), e.ivar[c * e.nx + d], z);
+  return z;
+}
+
 // mlp_tile for a general net: same inputs (S tile, xsh, tau, cmul, vec, bh in LDS), outputs and tile
 // orientation (hidden x path, wave = 16 paths, exact-fp32 v_mfma_f32_16x16x4_f32).  stash: this
 // workgroup's slot.
 // NET = NetGenHead: u and grad u are output columns (sh.bh[0 .. nxp) holds bg); stash is unused.
-template <int KIND, int HCAP, int ACT, class NET>
+// TERMA: the terminal ansatz around the net's outputs; sh.bsh[pp] holds T - s of path pp on entry (the
+// caller overwrites it after the call, from this wave).
+template <int KIND, int HCAP, int ACT, class NET, bool TERMA = false>
 __device__ __forceinline__ void mlp_tile_gen(const EqDev& e, const NET& net, LdsGen<HCAP>& sh, floatx4* stash,
                                              float& u_out, float& gsum_out, float& gA_out, float& gB_out) {
   constexpr bool HEAD = std::is_same_v<NET, NetGenHead>;
@@ -202,6 +255,17 @@ __device__ __forceinline__ void mlp_tile_gen(const EqDev& e, const NET& net, Lds
         if (!Eq<KIND>::GRAD_FULL) gp = fmaf(sh.vec[3 * H + h], a0[T][r], gp);
       }
     u_out = net.value ? qsum(up) + net.bout : 0.f;
+    [[maybe_unused]] float tms = 0.f, rc[NSG];
+    if constexpr (TERMA) {  // an OnlyGradient head: u = 0, grad u = grad g + (T - s) (G a_L + bg)
+      tms = sh.bsh[pp];
+      const float g = term_g<KIND>(e, sh, pp, qq, cm, rc);
+      u_out = 0.f;
+      if (!Eq<KIND>::GRAD_FULL) {
+        gsum_out = fmaf(tms, qsum(gp) + net.bgsum, (float)e.nx * (e.cha_k * g * (1.0f - g)));
+        gA_out = gB_out = 0.f;
+        return;
+      }
+    }
     if (!Eq<KIND>::GRAD_FULL) {  // sum_d u_x[d] = cg . a_L + sum_d bg[d]
       gsum_out = qsum(gp) + net.bgsum;
       gA_out = gB_out = 0.f;
@@ -220,7 +284,9 @@ __device__ __forceinline__ void mlp_tile_gen(const EqDev& e, const NET& net, Lds
             const int d = 16 * (T0 + T2) + 4 * qq + r;
             if (d < e.nx) {
               const float X = fmaf(cm, sh.S[d * SS + pp], sh.xsh[d]);
-              Eq<KIND>::gacc(e, d, X, acc[r] + sh.bh[d], A, B);
+              float z = acc[r] + sh.bh[d];
+              if constexpr (TERMA) z = fmaf(tms, z, term_dg(e, d, X, rc));
+              Eq<KIND>::gacc(e, d, X, z, A, B);
             }
           }
         }
@@ -242,6 +308,7 @@ __device__ __forceinline__ void mlp_tile_gen(const EqDev& e, const NET& net, Lds
       a0[T][r] = w * Act<ACT>::d(a0[T][r]);
     }
   u_out = qsum(up) + net.bout;
+  [[maybe_unused]] float tms = 0.f, gterm = 0.f, rc[NSG];
   // ---------------- backward: delta_l = (W_{l+1}^T delta_{l+1}) * act'(a_l)
 #pragma unroll 1
   for (int l = L - 2; l >= 0; --l) {
@@ -266,6 +333,11 @@ __device__ __forceinline__ void mlp_tile_gen(const EqDev& e, const NET& net, Lds
 #pragma unroll
       for (int r = 0; r < 4; ++r) a0[T][r] = a1[T][r];
   }
+  if constexpr (TERMA) {  // u = g + (T - s) N, grad u = grad g + (T - s) grad N
+    tms = sh.bsh[pp];
+    gterm = term_g<KIND>(e, sh, pp, qq, cm, rc);
+    u_out = fmaf(tms, u_out, gterm);
+  }
   // ---------------- input gradient
   if (!Eq<KIND>::GRAD_FULL) {
     float gp = 0.f;
@@ -274,6 +346,7 @@ __device__ __forceinline__ void mlp_tile_gen(const EqDev& e, const NET& net, Lds
 #pragma unroll
       for (int r = 0; r < 4; ++r) gp = fmaf(sh.vec[3 * H + 16 * T + 4 * qq + r], a0[T][r], gp);
     gsum_out = qsum(gp);
+    if constexpr (TERMA) gsum_out = fmaf(tms, gsum_out, (float)e.nx * (e.cha_k * gterm * (1.0f - gterm)));
     gA_out = gB_out = 0.f;
   } else {
     float A = 0.f, B = 0.f;
@@ -290,7 +363,9 @@ __device__ __forceinline__ void mlp_tile_gen(const EqDev& e, const NET& net, Lds
           const int d = 16 * (T0 + T2) + 4 * qq + r;
           if (d < e.nx) {
             const float X = fmaf(cm, sh.S[d * SS + pp], sh.xsh[d]);
-            Eq<KIND>::gacc(e, d, X, acc[r], A, B);
+            float z = acc[r];
+            if constexpr (TERMA) z = fmaf(tms, z, term_dg(e, d, X, rc));
+            Eq<KIND>::gacc(e, d, X, z, A, B);
           }
         }
       }
@@ -328,7 +403,11 @@ __device__ __forceinline__ float gen_matvec(const float* __restrict__ Wt, const 
   return y0 + y1;
 }
 // NET = NetGenHead (k_baseline_head): u and grad u at the point itself from the output columns.
-template <int KIND, class NET>
+// TERMA: the terminal ansatz at the point, u = g(x) + (T - t) N and grad g(x) + (T - t) grad N (a head:
+// its gradient rows, u = 0); thread 0 leaves g(x) in redn[0][0] and the OU responsibilities (from fp64
+// statistics of their own) in redn[1], which nobody reads after the g(x) reduction, and the first layer's
+// barrier publishes them.
+template <int KIND, class NET, bool TERMA = false>
 __device__ __forceinline__ void baseline_gen_body(const EqDev& e, const NET& net, const float* __restrict__ tx, int n,
                                                   float* __restrict__ gx, float* __restrict__ fb,
                                                   float* __restrict__ bx, const SampleSpec& smp,
@@ -389,7 +468,36 @@ __device__ __forceinline__ void baseline_gen_body(const EqDev& e, const NET& net
         for (int w = 0; w < NT / 64; ++w) a += bs.redn[w][c];
         st[c] = a;
       }
-      gx[i] = Eq<KIND>::gfin(e, st);
+      const float g = Eq<KIND>::gfin(e, st);
+      gx[i] = g;
+      if constexpr (TERMA && !Eq<KIND>::GRAD_FULL) bs.redn[0][0] = g;
+    }
+  }
+  if constexpr (TERMA && Eq<KIND>::GRAD_FULL) {  // g(x) and the responsibilities from fp64 statistics (gfin_w)
+    static_assert(NT / 64 >= 2, "redn[1] holds the responsibilities");
+    __shared__ double redd[NT / 64][NSG];
+    double sd[NSG];
+#pragma unroll
+    for (int c = 0; c < NSG; ++c) sd[c] = 0.0;
+    for (int d = tid; d < nx; d += NT) Eq<KIND>::gstat_d(e, d, bs.xs[d], sd);
+#pragma unroll
+    for (int c = 0; c < NSG; ++c) sd[c] = wave_sum_d(sd[c]);
+    if ((tid & 63) == 0)
+#pragma unroll
+      for (int c = 0; c < NSG; ++c) redd[tid >> 6][c] = sd[c];
+    __syncthreads();  // thread 0 is past its reads of redn
+    if (tid == 0) {
+      float rc[NSG];
+#pragma unroll
+      for (int c = 0; c < NSG; ++c) {
+        double a = 0.0;
+#pragma unroll
+        for (int w = 0; w < NT / 64; ++w) a += redd[w][c];
+        sd[c] = a;
+      }
+      bs.redn[0][0] = Eq<KIND>::gfin_w(e, sd, rc);
+#pragma unroll
+      for (int c = 0; c < NSG; ++c) bs.redn[1][c] = rc[c];
     }
   }
   const int H = net.H, L = net.L, nxp = net.nxp, hu = 16 * net.ht;  // hu: units in use
@@ -407,19 +515,33 @@ __device__ __forceinline__ void baseline_gen_body(const EqDev& e, const NET& net
     if (tid < H) bs.act[l][tid] = act_f(net.act, acc + net.b[l][tid]);
     __syncthreads();
   }
+  // the ansatz's factors (the layers' barriers published redn)
+  [[maybe_unused]] float tmt = 0.f, gterm = 0.f, rc[NSG];
+  if constexpr (TERMA) {
+    tmt = e.T - t;
+    gterm = bs.redn[0][0];
+#pragma unroll
+    for (int c = 0; c < NSG; ++c) rc[c] = Eq<KIND>::GRAD_FULL ? bs.redn[1][c] : 0.f;
+  }
   if constexpr (HEAD) {
     const float* const aL = bs.act[L - 1];
-    const float u = net.value ? block_sum_n<NT>(tid < H ? net.wout[tid] * aL[tid] : 0.f, bs.red) + net.bout : 0.f;
+    float u = net.value ? block_sum_n<NT>(tid < H ? net.wout[tid] * aL[tid] : 0.f, bs.red) + net.bout : 0.f;
+    if constexpr (TERMA) u = 0.f;
     float gs = 0.f, gA = 0.f, gB = 0.f;
     if (!Eq<KIND>::GRAD_FULL) {
       gs = block_sum_n<NT>(tid < H ? net.c1[tid] * aL[tid] : 0.f, bs.red) + net.bgsum;
+      if constexpr (TERMA) gs = fmaf(tmt, gs, (float)nx * (e.cha_k * gterm * (1.0f - gterm)));
     } else {  // one wave per row of G (coalesced in the unit), rows in a fixed order
       float A = 0.f, B = 0.f;
       for (int d = tid >> 6; d < nx; d += NT / 64) {
         float z = 0.f;
         for (int k = tid & 63; k < hu; k += 64) z = fmaf(net.G[(size_t)d * H + k], aL[k], z);
         z = wave_sum(z);
-        if ((tid & 63) == 0) Eq<KIND>::gacc(e, d, bs.xs[d], z + net.bg[d], A, B);
+        if ((tid & 63) == 0) {
+          z += net.bg[d];
+          if constexpr (TERMA) z = fmaf(tmt, z, term_dg(e, d, bs.xs[d], rc));
+          Eq<KIND>::gacc(e, d, bs.xs[d], z, A, B);
+        }
       }
       gA = block_sum_n<NT>(A, bs.red);
       gB = block_sum_n<NT>(B, bs.red);
@@ -427,7 +549,8 @@ __device__ __forceinline__ void baseline_gen_body(const EqDev& e, const NET& net
     if (tid == 0) fb[i] = Eq<KIND>::ffv(e, u, gs, gA, gB);
     return;
   }
-  const float u = block_sum_n<NT>(tid < H ? net.wout[tid] * bs.act[L - 1][tid] : 0.f, bs.red) + net.bout;
+  float u = block_sum_n<NT>(tid < H ? net.wout[tid] * bs.act[L - 1][tid] : 0.f, bs.red) + net.bout;
+  if constexpr (TERMA) u = fmaf(tmt, u, gterm);
   int cur = 0;
   if (tid < H) bs.dbuf[0][tid] = net.wout[tid] * act_d(net.act, bs.act[L - 1][tid]);
   __syncthreads();
@@ -440,11 +563,13 @@ __device__ __forceinline__ void baseline_gen_body(const EqDev& e, const NET& net
   float gs = 0.f, gA = 0.f, gB = 0.f;
   if (!Eq<KIND>::GRAD_FULL) {
     gs = block_sum_n<NT>(tid < H ? net.c1[tid] * bs.dbuf[cur][tid] : 0.f, bs.red);
+    if constexpr (TERMA) gs = fmaf(tmt, gs, (float)nx * (e.cha_k * gterm * (1.0f - gterm)));
   } else {
     float A = 0.f, B = 0.f;
     for (int d = tid; d < nx; d += NT) {
       float z = 0.f;
       for (int k = 0; k < hu; ++k) z = fmaf(net.W1x[(size_t)k * nxp + d], bs.dbuf[cur][k], z);
+      if constexpr (TERMA) z = fmaf(tmt, z, term_dg(e, d, bs.xs[d], rc));
       Eq<KIND>::gacc(e, d, bs.xs[d], z, A, B);
     }
     gA = block_sum_n<NT>(A, bs.red);
@@ -463,6 +588,20 @@ __global__ __launch_bounds__(NTB) void k_baseline_head(EqDev e, NetGenHead net, 
                                                       float* __restrict__ gx, float* __restrict__ fb,
                                                       float* __restrict__ bx, SampleSpec smp, int* __restrict__ tickets) {
   baseline_gen_body<KIND>(e, net, tx, n, gx, fb, bx, smp, tickets);
+}
+// The terminal-enforcing forms (TERMA): kernels of their own.
+template <int KIND>
+__global__ __launch_bounds__(NTB) void k_baseline_term(EqDev e, NetGen net, const float* __restrict__ tx, int n,
+                                                      float* __restrict__ gx, float* __restrict__ fb,
+                                                      float* __restrict__ bx, SampleSpec smp, int* __restrict__ tickets) {
+  baseline_gen_body<KIND, NetGen, true>(e, net, tx, n, gx, fb, bx, smp, tickets);
+}
+template <int KIND>
+__global__ __launch_bounds__(NTB) void k_baseline_head_term(EqDev e, NetGenHead net, const float* __restrict__ tx,
+                                                           int n, float* __restrict__ gx, float* __restrict__ fb,
+                                                           float* __restrict__ bx, SampleSpec smp,
+                                                           int* __restrict__ tickets) {
+  baseline_gen_body<KIND, NetGenHead, true>(e, net, tx, n, gx, fb, bx, smp, tickets);
 }
 
 }  // namespace dpi

@@ -724,8 +724,10 @@ int dpi_net_status_peek(dpi_net net, int slot, int* status) {
   return 0;
 }
 
-int dpi_net_create_mlp(int n_in, int n_hidden, const int* widths, int act, const float* params, size_t n_params,
-                       dpi_net* out) {
+// gen_only: the general image alone, whatever the shape (a terminal-enforcing value net has no
+// specialised instance)
+static int mlp_create(int n_in, int n_hidden, const int* widths, int act, const float* params, size_t n_params,
+                      dpi_net* out, bool gen_only) {
   if (n_in - 1 > NXW_MAX)
     return fail(DPI_ERR_UNSUPPORTED, "mlp: nx = n_in - 1 exceeds the compiled maximum state dimension 256 (NXW_MAX)");
   if (!out || !widths || !params || n_in < 2 || n_hidden < 1) return fail(DPI_ERR_ARG, "mlp: bad arguments");
@@ -751,7 +753,7 @@ int dpi_net_create_mlp(int n_in, int n_hidden, const int* widths, int act, const
   const float* const given = params;  // the finiteness scan (range guard) reads the caller's values
   const int H = wmax <= 16 ? 16 : wmax <= 32 ? 32 : wmax <= 64 ? 64 : wmax <= 128 ? 128 : 256;
   const int nx = n_in - 1, L = n_hidden;
-  const bool spec = L <= 4 && wmax <= HMAX;                 // the specialised image (NetDev)
+  const bool spec = !gen_only && L <= 4 && wmax <= HMAX;    // the specialised image (NetDev)
   const bool gen = !spec || !spec_shape(DPI_EQ_CHA, H, L);  // the general image (NetGen); Cha and OU share a list
   // nx padded to 16 (the fp32 weight images) and to 32 (the split ones).  The split layer-1 rows are
   // LDS chunks of at most 128 words whose 16-B granules are XOR-swizzled by row (split_swz): a closed
@@ -948,6 +950,32 @@ int dpi_net_create_mlp(int n_in, int n_hidden, const int* widths, int act, const
     dpi_net_destroy(n);
     return rc;
   }
+  *out = n;
+  return 0;
+}
+
+int dpi_net_create_mlp(int n_in, int n_hidden, const int* widths, int act, const float* params, size_t n_params,
+                       dpi_net* out) {
+  return mlp_create(n_in, n_hidden, widths, act, params, n_params, out, false);
+}
+
+// A terminal-enforcing net (include/dpi.h): the value net's or the OnlyGradient head's general image,
+// marked so that the pair routes to the TERMA kernels (dpi_general.h).
+int dpi_net_create_mlp_terminal(int n_in, int n_hidden, const int* widths, int act, int head, double T,
+                                const float* params, size_t n_params, dpi_net* out) {
+  if (head == DPI_HEAD_VALUE_GRADIENT)
+    return fail(DPI_ERR_ARG, "mlp_terminal: a terminal-enforcing net is DPI_HEAD_VALUE or DPI_HEAD_GRADIENT; the "
+                             "reference raises ValueError for ValueGradient (picard/solution_enforce_terminal.py:18-19)");
+  if (head != DPI_HEAD_VALUE && head != DPI_HEAD_GRADIENT)
+    return fail(DPI_ERR_ARG, "mlp_terminal: head must be DPI_HEAD_VALUE or DPI_HEAD_GRADIENT");
+  if (!(T > 0.0) || !std::isfinite(T)) return fail(DPI_ERR_ARG, "mlp_terminal: T must be positive and finite");
+  if (!out) return fail(DPI_ERR_ARG, "mlp: bad arguments");
+  dpi_net n = nullptr;
+  const int rc = head == DPI_HEAD_VALUE ? mlp_create(n_in, n_hidden, widths, act, params, n_params, &n, true)
+                                        : dpi_net_create_mlp_head(n_in, n_hidden, widths, act, head, params, n_params, &n);
+  if (rc) return rc;
+  n->term = true;
+  n->term_T = (float)T;
   *out = n;
   return 0;
 }
@@ -1756,6 +1784,18 @@ static bool runs_general(const dpi_problem_s* p, const dpi_net_s* net) {
 }
 // The general family's refusals, each naming its cap.  td: the call uses the TD estimators.
 static int general_refusal(const dpi_problem_s* p, const dpi_net_s* net, bool td, bool hess) {
+  if (net->term) {  // a terminal-enforcing net: the general family whatever its widths
+    const char* pre = "a terminal-enforcing network (PicardSolutionEnforceTerminal) runs the general MLP family, which ";
+    if (p->e.kind == DPI_EQ_GBM)
+      return fail(DPI_ERR_UNSUPPORTED, std::string(pre) + "serves Cha and OU problems only: GBM has no terminal-enforcing "
+                                                          "instance");
+    if (hess) return fail(DPI_ERR_UNSUPPORTED, std::string(pre) + "has no Hessian labels");
+    if (p->e.nx > NXP_MAX)
+      return fail(DPI_ERR_UNSUPPORTED, std::string(pre) + "is compiled for nx <= 128 (NXP_MAX)");
+    if (td)
+      return fail(DPI_ERR_UNSUPPORTED, std::string(pre) + "has no TD estimators (ESTIMATE_DELTA_T > 0)");
+    return 0;
+  }
   if (net->head) {  // a gradient head: the general family whatever its widths
     const char* pre = "a ValueGradient / OnlyGradient network (a gradient head) runs the general MLP family, which ";
     if (p->e.kind == DPI_EQ_GBM)
@@ -1788,7 +1828,7 @@ static bool dispatch_any(const dpi_problem_s* p, const dpi_net_s* net, const Lau
     // head nets: the baseline unit, or the path unit of the image's width cap
     const int head = !q.head ? 0 : q.baseline ? HEAD_BASE : net->g.H;
     for (const Unit& u : UNITS)
-      if (u.is(p->e.kind, false, tanh_g ? DPI_ACT_TANH : DPI_ACT_ELU, false, NXP_MAX, true, head))
+      if (u.is(p->e.kind, false, tanh_g ? DPI_ACT_TANH : DPI_ACT_ELU, false, NXP_MAX, true, head, q.term))
         return u.dispatch(p, net, q);
     return false;
   }
@@ -1829,6 +1869,7 @@ static Launch baseline_launch(const float* tx, int n, void* ws, const WsLayout& 
 static void route_launch(Launch& q, dpi_problem p, dpi_net net, void* ws, const WsLayout& w) {
   q.gen = runs_general(p, net);
   q.head = q.gen && net->head;
+  q.term = q.gen && net->term;
   if (q.gen && !q.baseline && !q.head) q.stash = (floatx4*)((char*)ws + w.stash);
 }
 static Launch path_launch(const PathArgs& a, int nblocks, hipStream_t st) {
@@ -1847,7 +1888,11 @@ static int check_pair(dpi_problem p, dpi_net net) {
   if (net->d.kind && net->d.nxp > NXW_MAX) return fail(DPI_ERR_ARG, "nx too large");
   if (p->e.nx > NXP_MAX && net->d.kind == 2)
     return fail(DPI_ERR_UNSUPPORTED, "PISGradNet: nx exceeds the compiled maximum state dimension 128 (NXP_MAX)");
-  if (runs_general(p, net)) return general_refusal(p, net, p->td_dt > 0.f, false);
+  if (runs_general(p, net)) {
+    if (int rc = general_refusal(p, net, p->td_dt > 0.f, false)) return rc;
+  }
+  if (net->term && net->term_T != p->e.T)
+    return fail(DPI_ERR_ARG, "the terminal-enforcing net was built for another T than the problem's");
   return 0;
 }
 
@@ -2548,7 +2593,7 @@ int dpi_generate_with_gradients_and_hessians(dpi_problem p, dpi_net net, const f
                                              float* y, void* ws, size_t ws_bytes, void* stream) {
   int rc = check_pair(p, net);
   if (rc) return rc;
-  if (net->head) return general_refusal(p, net, false, true);  // a gradient head has no Hessian labels
+  if (net->head || net->term) return general_refusal(p, net, false, true);  // no Hessian labels
   if (n < 0 || (!y && n) || M < 1 || M > 1024 * P)
     return fail(DPI_ERR_ARG, "generate_with_gradients_and_hessians: bad arguments (1 <= M <= 65536)");
   if (n == 0) return 0;

@@ -27,7 +27,7 @@ import torch
 from . import _lib
 from .dataset import IterableDatasetWithInternalBatch
 from .equations import Equation, OUProcessEquation, SimpleDiffusionEquation, SimpleDiffusionEquationWithHessian
-from .solution import DeviceNet
+from .solution import DeviceNet, ansatz_of, check_ansatz_equation
 
 # paths one label call takes (include/dpi.h DPI_PATHS_PER_CALL_MAX); more run as several calls
 PATHS_PER_CALL_MAX = _lib.DPI_PATHS_PER_CALL_MAX
@@ -310,6 +310,9 @@ class OnlineDataGenerator:
         for p in solution.parameters():  # data.py:409-412
             p.requires_grad = False
         solution.eval()
+        term, _ = ansatz_of(solution)
+        if term is not None:  # the kernels enforce this generator's g and T
+            check_ansatz_equation(term, equation)
         self.net = DeviceNet.from_module(solution, 1 + equation.nx)
         self.problem = equation.dpi_problem()
         self.sdgd_v = sdgd_v

@@ -29,7 +29,8 @@ from .data import OnlineDataGenerator
 from .dataset import TensorDatasetBuiltInShuffle
 from .fit import build_objective, make_optimizer, train_steps
 from .sharding import ShardedLabeler
-from .solution import OUTPUT_DIM, PISGradNet, ZeroSolution, construct_mlp, head_columns
+from .solution import (OUTPUT_DIM, TERMINAL_CLS, TERMINAL_HEADS, PicardSolutionEnforceTerminal, PISGradNet, ZeroSolution,
+                       construct_mlp, head_columns)
 
 
 class LabelBuffer:
@@ -123,7 +124,10 @@ class PicardRunner:
             warnings.warn("DATA.FLOAT: double — the device label path computes in fp32 (labels within the "
                           "north star's rel-L2 <= 1e-4 of the fp64 reference, DESIGN.md); the fit and the "
                           "label files follow DATA.FLOAT", stacklevel=2)
-        if cfg.METHOD.cls != "Picard":  # Diffusion / PINN / FullyNonlinearSolver baselines: out of scope
+        # picard_iteration.py:253-264: PINN, Diffusion and FullyNonlinearSolver are the baselines' own
+        # loops (out of scope); every other METHOD.cls (Picard, OptimalControl, DeepNesting, ...) takes the
+        # Picard path
+        if cfg.METHOD.cls in ("PINN", "Diffusion", "FullyNonlinearSolver"):
             raise NotImplementedError(f"METHOD.cls={cfg.METHOD.cls}: only the DPI (Picard) method is built")
         if cfg.PICARD.FORMULA == "TwoLayer":
             raise NotImplementedError("PICARD.FORMULA=TwoLayer is out of scope")
@@ -141,6 +145,20 @@ class PicardRunner:
         if self.output_dim != 1 and self.supervise_hessian:
             raise NotImplementedError(f"TRAIN.SUPERVISE_HESSIAN with NETWORK.TYPE={cfg.NETWORK.TYPE}: Hessian labels "
                                       "and Hessian supervision of a gradient head are out of scope")
+        # NETWORK.cls (picard_iteration.py:93-102 get_solution_cls): the solution class around the network
+        self.solution_cls = cfg.NETWORK.cls or "PicardSolution"
+        if self.solution_cls not in ("PicardSolution", TERMINAL_CLS):
+            raise ValueError(f"Unknown solution class {self.solution_cls}")
+        if self.solution_cls == TERMINAL_CLS:
+            if cfg.NETWORK.TYPE not in TERMINAL_HEADS:  # solution_enforce_terminal.py:18-19
+                raise ValueError(f"Unsupported network configuration: {TERMINAL_CLS} with NETWORK.TYPE="
+                                 f"{cfg.NETWORK.TYPE} (Value or OnlyGradient)")
+            if cfg.NETWORK.PISGRADNET:
+                raise NotImplementedError(f"NETWORK.PISGRADNET with NETWORK.cls={TERMINAL_CLS}: the label kernels have "
+                                          "the terminal-enforcing ansatz for construct_mlp networks only")
+            if self.supervise_hessian:
+                raise NotImplementedError(f"TRAIN.SUPERVISE_HESSIAN with NETWORK.cls={TERMINAL_CLS}: a "
+                                          "terminal-enforcing network has no Hessian labels")
         self.N = cfg.PICARD.N
         self.i = 0
         self.u_current = ZeroSolution(self.output_dim)
@@ -168,6 +186,8 @@ class PicardRunner:
             net = PISGradNet(hidden_shapes=list(c.NEURONS), dim=self.equation.nx, g0=self.equation.g, T=self.equation.T)
         else:
             net = construct_mlp(1 + self.equation.nx, self.output_dim, list(c.NEURONS), list(c.ACTIVATIONS), c.BOUND)
+        if self.solution_cls == TERMINAL_CLS:  # fit, evaluation, checkpoints and labels run on the wrapper
+            net = PicardSolutionEnforceTerminal(self.equation, net, c.TYPE)
         return net.to(self.device)
 
     def checkpoint_path(self, i):

@@ -103,11 +103,82 @@ class PISGradNet(torch.nn.Module):
         return smooth * sp_out + (1.0 - smooth) * residual
 
 
+TERMINAL_CLS = "PicardSolutionEnforceTerminal"
+# NETWORK.TYPE of a terminal-enforcing solution -> the DPI_HEAD_* of its inner network
+# (picard/solution_enforce_terminal.py:14-19: ValueGradient raises there)
+TERMINAL_HEADS = {"Value": _lib.DPI_HEAD_VALUE, "OnlyGradient": _lib.DPI_HEAD_GRADIENT}
+
+
+class PicardSolutionEnforceTerminal(torch.nn.Module):
+    """picard/solution_enforce_terminal.py:9-27 — the hard-constraint ansatz around a construct_mlp net
+    `model`, with u(T, .) = g by construction:
+        type "Value":         u(t, x)   = g(x)   + (T - t) model(t, x)
+        type "OnlyGradient":  out(t, x) = g_x(x) + (T - t) model(t, x)   (nx outputs, read as u_x; u = 0)
+    Submodule `.model` and buffer `T` as in the reference, so its state dict loads unchanged."""
+
+    def __init__(self, equation, model, type="Value"):
+        super().__init__()
+        if type not in TERMINAL_HEADS:  # solution_enforce_terminal.py:18-19
+            raise ValueError(f"Unsupported network configuration: {TERMINAL_CLS} with NETWORK.TYPE={type} "
+                             "(Value or OnlyGradient)")
+        self.equation = equation
+        self.model = model
+        self.net_type = type  # (nn.Module.type is a method)
+        self.register_buffer("T", torch.scalar_tensor(float(equation.T)))
+
+    def forward(self, tx):
+        t, x = torch.narrow(tx, -1, 0, 1), torch.narrow(tx, -1, 1, self.equation.nx)
+        g = self.equation.g(x) if self.net_type == "Value" else self.equation.g_x(x)
+        return g + (self.T - t) * self.model(tx)
+
+
+def ansatz_of(module):
+    """(wrapper, type) of the terminal-enforcing solution inside `module` — this build's
+    PicardSolutionEnforceTerminal or the reference's class of that name, bare or inside a
+    PicardSolutionGradientWrapper's `.solution` — or (None, None).  Host only: no device, no library.
+    The reference's class keeps no type attribute: its type is the form it bound to `forward`."""
+    while isinstance(module, torch.nn.Module):
+        if isinstance(module, PicardSolutionEnforceTerminal):
+            return module, module.net_type
+        if type(module).__name__ == TERMINAL_CLS:
+            # the form its constructor bound to `forward` (solution_enforce_terminal.py:14-17); a look-alike
+            # without it: network_cfg.TYPE
+            kind = {"_forward_value": "Value", "_forward_with_gradient": "OnlyGradient"}.get(
+                getattr(module.forward, "__name__", None))
+            if kind is None:
+                cfg = getattr(module, "network_cfg", None)
+                kind = cfg.get("TYPE") if hasattr(cfg, "get") else getattr(cfg, "TYPE", None)
+            if kind not in TERMINAL_HEADS:
+                raise ValueError(f"Unsupported network configuration: {TERMINAL_CLS} with NETWORK.TYPE={kind} "
+                                 "(Value or OnlyGradient)")
+            return module, kind
+        inner = getattr(module, "model", None)
+        if not isinstance(inner, torch.nn.Module):
+            inner = getattr(module, "solution", None)
+        module = inner
+    return None, None
+
+
+def check_ansatz_equation(wrapper, equation):
+    """A terminal-enforcing solution carries the equation whose g and T it enforces; the label kernels
+    take both from the generator's equation.  ValueError unless the two agree in class name, nx and T
+    (values, not identity: through the reference-side binding the wrapper holds the reference's object)."""
+    weq = getattr(wrapper, "equation", None)
+    got = (type(weq).__name__, int(getattr(weq, "nx", -1)), float(getattr(weq, "T", float("nan"))))
+    want = (type(equation).__name__, int(equation.nx), float(equation.T))
+    if got != want:
+        raise ValueError(f"{TERMINAL_CLS} enforces the terminal condition of {got[0]}(nx={got[1]}, T={got[2]}) but the "
+                         f"generator's equation is {want[0]}(nx={want[1]}, T={want[2]})")
+
+
 def _unwrap(module):
     """The network inside the reference's solution wrappers: PicardSolution keeps it in `.model`
     (picard/solution.py:313-325), PicardSolutionGradientWrapper / ...HessianWrapper keep the
-    PicardSolution in `.solution` (picard/solution_jac.py:124-126, 219-226)."""
+    PicardSolution in `.solution` (picard/solution_jac.py:124-126, 219-226).  Stops at a
+    terminal-enforcing solution (ansatz_of): its `.model` alone is not the function it computes."""
     while True:
+        if isinstance(module, PicardSolutionEnforceTerminal) or type(module).__name__ == TERMINAL_CLS:
+            return module
         inner = getattr(module, "model", None)
         if not isinstance(inner, torch.nn.Module):
             inner = getattr(module, "solution", None)
@@ -191,6 +262,12 @@ class DeviceNet:
         lib = _lib.load()
         m = _unwrap(module)
         h = _lib.c_void_p()
+        term, term_type = ansatz_of(m)
+        if term is not None:  # upload the inner network; the kernels add g, grad g and the (T - t) factor
+            m = term.model
+            if not isinstance(m, torch.nn.Sequential):
+                raise NotImplementedError(f"{TERMINAL_CLS} around {type(m).__name__}: the label kernels have the "
+                                          "ansatz for construct_mlp networks only")
         if isinstance(m, ZeroSolution) or type(m).__name__ == "ZeroSolution":
             _lib.check(lib.dpi_net_create_zero(h), "dpi_net_create_zero")
             return cls(h, "zero")
@@ -208,11 +285,20 @@ class DeviceNet:
             if lin[0].in_features != n_in:
                 raise ValueError(f"network input {lin[0].in_features} != 1 + nx = {n_in}")
             head = head_of(lin[-1].out_features, n_in - 1)
+            if term is not None and head != TERMINAL_HEADS[term_type]:
+                raise ValueError(f"{TERMINAL_CLS} of NETWORK.TYPE {term_type}: the inner network has "
+                                 f"{lin[-1].out_features} outputs ({HEAD_NAMES[head]})")
             widths = [l.out_features for l in lin[:-1]]
             flat = np.concatenate([np.concatenate([l.weight.detach().cpu().double().numpy().ravel(),
                                                    l.bias.detach().cpu().double().numpy().ravel()]) for l in lin])
             flat = np.ascontiguousarray(flat, np.float32)
             w = (_lib.c_int * len(widths))(*widths)
+            if term is not None:
+                _lib.check(lib.dpi_net_create_mlp_terminal(n_in, len(widths), w, act_code, head, float(term.T),
+                                                           flat.ctypes.data_as(_lib.P(_lib.c_float)), flat.size, h),
+                           "dpi_net_create_mlp_terminal")
+                return cls(h, f"mlp{widths}" + ("" if act_code == _lib.DPI_ACT_ELU else "-tanh") + "-"
+                           + HEAD_NAMES[head] + "-terminal")
             if head != _lib.DPI_HEAD_VALUE:
                 # a gradient head (NETWORK.TYPE ValueGradient / OnlyGradient): grad u is an output, the
                 # labels run the general family's forward-only head kernels whatever the widths

@@ -18,6 +18,7 @@
  *   dpi_net_create_zero      picard/solution.py:330-337   ZeroSolution (iteration 1)
  *   dpi_net_create_mlp       picard/solution.py:123-135   construct_mlp (state-dict order)
  *   dpi_net_create_mlp_head  picard/solution.py:301-324, picard/data.py:1231-1242  NETWORK.TYPE ValueGradient / OnlyGradient
+ *   dpi_net_create_mlp_terminal  picard/solution_enforce_terminal.py:9-27  NETWORK.cls PicardSolutionEnforceTerminal
  *   dpi_net_create_pisgrad   picard/solution.py:138-289   PISGradNet (state-dict order)
  *   dpi_sample_points        picard/data.py:161-167, :211-217  sample_t_always_uniform + equation.sample_x
  *   dpi_sample_points_t      picard/data.py:149-159 (sample_t, t_always_uniform: false) or :161-167
@@ -151,6 +152,20 @@ int dpi_net_create_mlp(int n_in, int n_hidden, const int* widths, int act, const
 #define DPI_HEAD_GRADIENT 2
 int dpi_net_create_mlp_head(int n_in, int n_hidden, const int* widths, int act, int head, const float* params,
                             size_t n_params, dpi_net* out);
+/* The reference's PicardSolutionEnforceTerminal (NETWORK.cls; picard/solution_enforce_terminal.py:9-27)
+ * around construct_mlp's net N, the hard-constraint ansatz with u(T, .) = g by construction:
+ *   DPI_HEAD_VALUE     u(t, x) = g(x) + (T - t) N(t, x)                          (NETWORK.TYPE Value)
+ *   DPI_HEAD_GRADIENT  grad_x u = grad g(x) + (T - t) N(t, x), nx outputs; u = 0  (OnlyGradient)
+ * DPI_HEAD_VALUE_GRADIENT is DPI_ERR_ARG: the reference raises ValueError for ValueGradient
+ * (solution_enforce_terminal.py:18-19).  params, their order and the caps are dpi_net_create_mlp_head's;
+ * g and T are the problem's, and a label call on a problem whose T differs from this T fails with
+ * DPI_ERR_ARG.  Such a net holds the general image only (also at 4 x 128): first-order Cha / OU labels,
+ * nx <= 128, no TD, in the general MLP family (dpi_pair_family: DPI_FAMILY_GENERAL); GBM, the TD
+ * estimators, Hessian labels and nx > 128 are refused at the label call and by dpi_pair_family with
+ * DPI_ERR_UNSUPPORTED.  The Value form has the general family's stash (dpi_general_slots > 0), the
+ * OnlyGradient form none. */
+int dpi_net_create_mlp_terminal(int n_in, int n_hidden, const int* widths, int act, int head, double T,
+                                const float* params, size_t n_params, dpi_net* out);
 /* Which kernel family the label calls on (p, net) run (host only, no device work): *family =
  * DPI_FAMILY_SPECIALISED (also for zero and PISGradNet nets) or DPI_FAMILY_GENERAL, the general MLP
  * family, which is fp32 only: dpi_set_gemm_precision / dpi_net_set_precision select nothing for it.

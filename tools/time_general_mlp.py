@@ -9,7 +9,11 @@ and the gradient-head nets (NETWORK.TYPE ValueGradient / OnlyGradient, DESIGN.md
 8 x 256, which run the general family's forward-only head kernels.  One JSON line per net, and the LDS / register / workgroups-per-CU figures of the general kernels
 from the library's code objects.
 
-    python tools/time_general_mlp.py [--reps 30] [--warmup 5] [--act ELU]
+--ansatz: the terminal-enforcing solutions (NETWORK.cls PicardSolutionEnforceTerminal)
+instead — Cha and OU at nx = 100, [64] * 4 and [128] * 4: the plain Value and OnlyGradient routes (the
+yardsticks, in the same process) beside the terminal-enforcing Value and OnlyGradient forms.
+
+    python tools/time_general_mlp.py [--reps 30] [--warmup 5] [--act ELU] [--ansatz]
 """
 import argparse
 import json
@@ -40,10 +44,18 @@ def mlp_flops(widths, n_out=1):
     return 2 * f
 
 
-def time_net(widths, mode, act, reps, warmup, n_out=1):
+def equation(kind):
+    if kind == "cha":
+        return dpi.Cha(NX, 1.0, 5.0, 1.0)
+    return dpi.OUProcessEquation(nx=NX, T=1.0, alpha=1.0, num_components=5, mean_scale=1.0, var_scale=2.0, alpha_scale=4.0)
+
+
+def time_net(widths, mode, act, reps, warmup, n_out=1, eq_kind="cha", ansatz=False):
     torch.manual_seed(0)
-    eq = dpi.Cha(NX, 1.0, 5.0, 1.0)
+    eq = equation(eq_kind)
     net = dpi.construct_mlp(1 + NX, n_out, widths, [act] * len(widths), None)
+    if ansatz:
+        net = dpi.PicardSolutionEnforceTerminal(eq, net, "Value" if n_out == 1 else "OnlyGradient")
     gen = dpi.OnlineDataGenerator(eq, net, 1, 1, device="cuda:0", t_always_uniform=True, n_estimate_terminal=M,
                                   n_estimate_integral=M, n_euler_steps=K, seed=5)
     if mode is not None:
@@ -62,7 +74,8 @@ def time_net(widths, mode, act, reps, warmup, n_out=1):
         evs.append((a, b))
     torch.cuda.synchronize()
     t = sorted(a.elapsed_time(b) for a, b in evs)
-    return {"family": "general" if family == L.DPI_FAMILY_GENERAL else "specialised", "ms_median": t[len(t) // 2],
+    return {"family": "general" if family == L.DPI_FAMILY_GENERAL else "specialised", "desc": gen.net.desc,
+            "ms_median": t[len(t) // 2],
             "ms_min": t[0], "mlp_mflop_per_path": mlp_flops(widths, n_out) / 1e6, "stash_slots": gen.net.general_slots(),
             "workspace_mb": gen.workspace_bytes(N, M) / 2 ** 20}
 
@@ -72,13 +85,27 @@ def main():
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--act", default="ELU", choices=["ELU", "Tanh"])
+    ap.add_argument("--ansatz", action="store_true", help="the terminal-enforcing forms beside their plain routes")
     a = ap.parse_args()
     assert a.reps >= 20, "the median of at least 20 calls"
+    names = ("k_paths_term<", "k_baseline_term<", "k_paths_head_term<", "k_baseline_head_term<") if a.ansatz else \
+        ("k_paths_gen<", "k_baseline_gen<", "k_paths_head<", "k_baseline_head<")
     for k in kernel_resources():
-        if any(f in k["name"] for f in ("k_paths_gen<", "k_baseline_gen<", "k_paths_head<", "k_baseline_head<")):
+        if any(f in k["name"] for f in names):
             print(json.dumps({"kernel": k["name"].split("(")[0], "vgpr": k["vgpr_count"], "agpr": k["agpr_count"],
                               "lds_bytes": k["group_segment_fixed_size"], "sgpr_spill": k["sgpr_spill_count"],
                               "vgpr_spill": k["vgpr_spill_count"]}), flush=True)
+    if a.ansatz:
+        for eq_kind in ("cha", "ou"):
+            for widths in ([64] * 4, [128] * 4):
+                for n_out in (1, NX):
+                    for ansatz in (False, True):
+                        typ = "Value" if n_out == 1 else "OnlyGradient"
+                        name = f"{eq_kind} {len(widths)}x{widths[0]} {typ}" + (" terminal" if ansatz else " plain")
+                        print(json.dumps({"net": name, "act": a.act,
+                                          **time_net(widths, None, a.act, a.reps, a.warmup, n_out, eq_kind, ansatz)}),
+                              flush=True)
+        return
     for name, widths, mode, *n_out in NETS:
         print(json.dumps({"net": name, "act": a.act, **time_net(widths, mode, a.act, a.reps, a.warmup, *n_out)}),
               flush=True)

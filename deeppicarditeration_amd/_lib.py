@@ -20,6 +20,7 @@ DPI_HEAD_VALUE, DPI_HEAD_VALUE_GRADIENT, DPI_HEAD_GRADIENT = 0, 1, 2  # dpi_net_
 DPI_TERMINAL, DPI_INTEGRAL, DPI_BOTH = 1, 2, 3
 DPI_PREPARED = 4  # dpi_label_moments: dpi_label_prepare already ran with the same arguments
 DPI_PATH_BLOCK = 64
+DPI_PARK_MAX_BLOCKS = 2048  # path blocks up to which dpi_workspace_bytes holds a park row per block
 DPI_PATHS_PER_CALL_MAX = 1024 * DPI_PATH_BLOCK
 DPI_GEMM_F32, DPI_GEMM_F16X3, DPI_GEMM_AUTO = 0, 1, 2
 DPI_STATUS_NONFINITE = 1

@@ -73,6 +73,12 @@ constexpr int WST = 136;           // LDS row stride of a staged weight chunk (W
 // A/B knob, tools/build_variant.py)
 #define DPI_NOISE_TABLE_FO 1
 #endif
+#ifndef DPI_PHASE_STAMPS
+// 1: the diagnostic build of the parking path kernels (tools/build_variant.py, tools/phase_stamps.py):
+// every wave of a path block stamps its phase boundaries into the block's park row.  The product
+// executes no stamp.
+#define DPI_PHASE_STAMPS 0
+#endif
 constexpr int NXP_MAX = 128;       // max padded state dimension of the two-workgroups-per-CU path kernels
 // max state dimension of the wide first-order instances (Cha / OU, one workgroup per CU: the noise
 // tile of 256 dims x 64 paths is 70 KB of LDS; dpi_paths_wide_*.hip)
@@ -1848,7 +1854,14 @@ struct PathArgs {
   // GBM prepared calls (dpi_label_prepare): the noise sums of phase 1, already rolled out by
   // k_noise_shared beside the previous batch's path launch, [n][nbp][2 (terminal, integral)][4 nb][P]
   const float* noise;
+  // The park of the split first-order instances (paths_body PARK; null: all blocks run terminal-last):
+  // one row of PARK_ROW floats per path block of the call, indexed by the block id, in which a
+  // terminal-first block keeps its terminal sums across the MLP.
+  float* park;
 };
+// A park row: [wave 4][dim-block NXP_MAX / 16][lane 64][4] floats (32 KB), each wave's 16-B stores
+// and loads contiguous over its lanes.
+constexpr int PARK_ROW = 4 * (NXP_MAX / 16) * 64 * 4;
 
 // The fused per-point baseline of k_paths_fb (dpi_sample_with_gradients as one launch: first-order
 // Cha / OU labels of MLP and zero nets, no TD), an argument of that kernel only: blocks
@@ -2302,9 +2315,12 @@ __device__ __forceinline__ void paths_body(const EqDev& e, const NET& net, const
   //  - before the MLP: no wave's LDS-DMA (SplitStream::issue) or staged fp32 chunk may land in the
   //    ring while another wave still reads its table.  Every phase order has a workgroup barrier
   //    between its last rollout before the integrand and the integrand: the one after base_poll_
-  //    (terminal-last), terminal_finish's (terminal-first); the MLP's first write into the ring comes
-  //    after it.  The u = 0 instances never touch the ring.
-  //  - after the MLP (terminal-last order only): a wave that leaves the integrand builds its first
+  //    (terminal-last, and the parked terminal-first order of the split instances, whose last
+  //    rollout before the MLP is the integral one too), terminal_finish's (unparked terminal-first);
+  //    the MLP's first write into the ring, the stream's first LDS-DMA included, comes after it.  The
+  //    u = 0 instances never touch the ring.
+  //  - after the MLP (terminal-last order only; a parked terminal-first block builds no table after
+  //    the MLP, it reloads its sums): a wave that leaves the integrand builds its first
   //    terminal table while a slower wave may still read the ring's last chunk.  So the tables are
   //    the last 4 KB of the ring slot which that chunk does not occupy (ntab below).  Split MLP: chunk
   //    idx sits in slot idx & 1, so the last of SplitStream's `total` chunks leaves slot total & 1;
@@ -2314,7 +2330,9 @@ __device__ __forceinline__ void paths_body(const EqDev& e, const NET& net, const
   //    No barrier is added (one between the integrand and the terminal rollout measured 2 us slower
   //    per launch).
   // One instance keeps the plain form: the split OU 4 x 128 ELU k_paths, at 255 registers without the
-  // table, spills 6 VGPRs at 256 with it (and its occupancy is not lowered to make it fit).
+  // table, spills 6 VGPRs at 256 with it (and its occupancy is not lowered to make it fit).  For the
+  // same reason it parks nothing (PARK_SPILLS below: one VGPR spilled with the park's stores and
+  // loads) and keeps every block terminal-last whatever DPI_ORDER says.
   constexpr bool NOISE_TAB_SPILLS = KIND == DPI_EQ_OU && H == 128 && L == 4 && SPLIT && ACT == DPI_ACT_ELU;
   constexpr bool NOISE_TAB =
       DPI_NOISE_TABLE_FO && !GBM && !HESS && !TD && !GEN && NXW == NXP_MAX && !NOISE_TAB_SPILLS;
@@ -2524,13 +2542,16 @@ __device__ __forceinline__ void paths_body(const EqDev& e, const NET& net, const
     }
   };
   // g(X_T) statistics over the 4 waves in fixed order; the barrier also publishes S / fst
-  auto terminal_finish = [&]() -> float {
+  // (terminal_publish: this wave's part, which nothing overwrites before terminal_sum's barrier)
+  auto terminal_publish = [&]() {
 #pragma unroll
     for (int c = 0; c < NSG; ++c) sh.gst[(wv * P + lane) * NSG + c] = gst[c];
     if constexpr (GBM) {
 #pragma unroll
       for (int c = 0; c < NSG; ++c) sh.fst[(wv * P + lane) * NSG + c] = fst[c];
     }
+  };
+  auto terminal_sum = [&]() -> float {
     __syncthreads();
     float gT = 0.f;
     if (TERM) {
@@ -2541,6 +2562,10 @@ __device__ __forceinline__ void paths_body(const EqDev& e, const NET& net, const
       gT = Eq<KIND>::gfin(e, gst);
     }
     return TERM ? gT - g_x : 0.f;  // (g(X_T) - g(x)) (data.py:923)
+  };
+  auto terminal_finish = [&]() -> float {
+    terminal_publish();
+    return terminal_sum();
   };
 
   // ---------------- phase 2: u, grad u (or the SDGD Hessian diagonal) at (s, X_s) and f -> bsh
@@ -2607,13 +2632,37 @@ __device__ __forceinline__ void paths_body(const EqDev& e, const NET& net, const
   // order run the MLP between the integral and the terminal rollout, so a co-resident pair in
   // opposite orders overlaps one's MFMA phase with the other's VALU phase.  The results do not
   // depend on the order (same counters, same per-lane arithmetic).
+  // The split instances (nx <= 128, no TD) cannot hold the terminal sums across the MLP (254 VGPRs as
+  // it is), so their terminal-first blocks park them (PARK): after its terminal rollout a block
+  // stores ST to its row of a.park — lane = path, one 16-B store per dim-block, 1 KB contiguous per
+  // wave — and loads it back after the MLP, before phase 3.  Every lane reads what it wrote itself:
+  // no fence, the values go through memory unchanged.  Without a park (a.park null: more path blocks
+  // than DPI_PARK_MAX_BLOCKS, include/dpi.h) every block runs terminal-last as before; with one, by
+  // default (a.order 0, or 5) every block runs terminal-first: its two rollouts then run back to back
+  // with no barrier between them, so a wave's 7/6/6/6 terminal and 6/6/6/7 integral dim-blocks add
+  // up to 13/12/12/13 before the one barrier ahead of the MLP, and the barrier wait after the
+  // terminal rollout is gone (measured faster than pairing the orders).  a.order 1:
+  // the two workgroups of a CU in opposite orders by their workgroup slot, which a slot's successor
+  // inherits; 2, 3: by block index; 4: all terminal-last.  Whichever order: integral rollout,
+  // barrier, MLP once in the code.
+  // (NOISE_TAB_SPILLS' instance, at 255 registers, spills one with the park too: all terminal-last)
+  constexpr bool PARK_SPILLS = NOISE_TAB_SPILLS;
+  constexpr bool PARK = SPLIT && !GBM && !TD && !GEN && NXW == NXP_MAX && !PARK_SPILLS;
   bool tlast = false;
   if constexpr (TD) {
     tlast = false;  // the terminal MLP needs the noise tile before the integral rollout
   } else if constexpr (GEN) {
     tlast = true;  // the terminal sums are not live across the MLP (its two layers of registers)
   } else if constexpr (SPLIT && !GBM) {
-    tlast = true;  // measured faster, and the terminal sums are not live across the MLP (no spills)
+    tlast = true;  // the terminal sums are not live across the MLP (no spills)
+    if constexpr (PARK) {
+      if (a.park != nullptr) {
+        if (a.order == 1) tlast = (__builtin_amdgcn_s_getreg((3 << 11) | (16 << 6) | 4) & 1) != 0;  // HW_ID.TG_ID
+        else if (a.order == 2) tlast = (bid & 1) != 0;
+        else if (a.order == 3) tlast = ((bid >> 8) & 1) != 0;
+        else if (a.order != 4) tlast = false;
+      }
+    }
   } else if constexpr (!GBM) {
     if (a.order == 1) tlast = (__builtin_amdgcn_s_getreg((3 << 11) | (16 << 6) | 4) & 1) != 0;  // HW_ID.TG_ID
     else if (a.order == 2) tlast = (bid & 1) != 0;
@@ -2678,6 +2727,55 @@ __device__ __forceinline__ void paths_body(const EqDev& e, const NET& net, const
       }
     }
   };
+  // the park row of this block: this lane's 16 B of wave wv's dim-block c at prow[64 c]
+  [[maybe_unused]] auto park_row = [&]() -> floatx4* {
+    return reinterpret_cast<floatx4*>(a.park + (size_t)bid * PARK_ROW) + (wv * NBW) * 64 + lane;
+  };
+  [[maybe_unused]] auto park_store = [&]() {
+    floatx4* const prow = park_row();
+#pragma unroll
+    for (int c = 0; c < NBW; ++c)
+      if (TERM && wv + 4 * c < nb) prow[64 * c] = floatx4{ST[c][0], ST[c][1], ST[c][2], ST[c][3]};
+  };
+  [[maybe_unused]] auto park_load = [&]() {
+    const floatx4* const prow = park_row();
+#pragma unroll
+    for (int c = 0; c < NBW; ++c) {
+      floatx4 v = {0.f, 0.f, 0.f, 0.f};
+      if (TERM && wv + 4 * c < nb) v = prow[64 * c];
+      ST[c][0] = v[0];
+      ST[c][1] = v[1];
+      ST[c][2] = v[2];
+      ST[c][3] = v[3];
+    }
+  };
+  // DPI_PHASE_STAMPS: lane 0 of every wave stores the clock at phase boundary k to the park row's
+  // last dim-block of wave 0, which no wave parks at nx <= 112 (the stamps are off above that):
+  // 64-bit words [0] HW_ID | XCC_ID << 32, [1] the order, [4 + 8 wave + k] the stamps.
+  [[maybe_unused]] auto stamp = [&](int k) {
+#if DPI_PHASE_STAMPS
+    if constexpr (PARK) {
+      if (a.park != nullptr && nb <= 28) {
+        unsigned long long tk;
+        __builtin_amdgcn_sched_barrier(0);
+        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(tk)::"memory");
+        __builtin_amdgcn_sched_barrier(0);
+        unsigned long long* const sp =
+            reinterpret_cast<unsigned long long*>(a.park + (size_t)bid * PARK_ROW + (NBW - 1) * 64 * 4);
+        if (lane == 0) {
+          sp[4 + 8 * wv + k] = tk;
+          if (k == 0 && wv == 0) {
+            sp[0] = (unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 4) |
+                    ((unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 20) << 32);  // HW_ID, XCC_ID
+            sp[1] = tlast ? 1ull : 0ull;
+          }
+        }
+      }
+    }
+#else
+    (void)k;
+#endif
+  };
   float ap;
   if constexpr (TD) {
     terminal_rollout();
@@ -2688,6 +2786,31 @@ __device__ __forceinline__ void paths_body(const EqDev& e, const NET& net, const
     if (td_u) ap = TERM ? uT - g_x : 0.f;  // (u(t_next, X) - g(x)) (data.py:942, :947)
     integrand();
     __syncthreads();
+  } else if constexpr (PARK) {
+    stamp(0);
+    if (!tlast) {
+      terminal_rollout();
+      park_store();
+      terminal_publish();
+      stamp(1);
+    }
+    integral_rollout();
+    stamp(2);
+    base_poll_();
+    __syncthreads();
+    base_load();
+    stamp(3);
+    integrand();
+    stamp(4);
+    if (tlast) {
+      terminal_rollout();
+      terminal_publish();
+    } else {
+      park_load();
+    }
+    stamp(5);
+    ap = terminal_sum();  // its barrier also publishes bsh
+    stamp(6);
   } else if (!tlast) {
     terminal_rollout();
     integral_rollout();
@@ -2827,6 +2950,7 @@ __device__ __forceinline__ void paths_body(const EqDev& e, const NET& net, const
   } else {
     if (a.tickets) fused_reduce(a, i, F, FB ? fb.rec : nullptr);
   }
+  stamp(7);
 }
 
 template <int KIND, int H, int L, bool ZERO, bool SPLIT, bool HESS = false, bool TD = false, int ACT = DPI_ACT_ELU,

@@ -1430,10 +1430,11 @@ static int pis_chunk_wg() {
 }
 
 // Workspace: gx[n] | fb[n] | bx[n][H] | hb[n][HBS = 256] | tickets[n] | rec[n][BREC] | ready[n] |
-// [PIS rows] | partial[n][nbp][slab_row] | ... | [stash]  (256-B aligned)
+// [PIS rows] | partial[n][nbp][slab_row] | ... | [stash] | [park]  (256-B aligned)
 struct WsLayout {
-  size_t gx, fb, bx, hb, tk, rec, ready, rows, partial, rq, noise, nq, stash, total;
+  size_t gx, fb, bx, hb, tk, rec, ready, rows, partial, rq, noise, nq, stash, park, total;
   int rows_cap;
+  size_t park_rows;  // rows of the park region (0: none)
 };
 static size_t al256(size_t x) { return (x + 255) & ~size_t(255); }
 // GBM MLP nets stage their noise sums on the prepare stream (dpi_label_prepare -> k_noise_shared;
@@ -1442,7 +1443,12 @@ static bool gbm_noise_prep(dpi_problem p, dpi_net net) {
   static const bool on = env_int("DPI_GBM_PREP", 1) != 0;
   return on && p && net && net->d.kind == 1 && p->e.kind == DPI_EQ_GBM;
 }
-static WsLayout ws_layout(dpi_net net, int n, int M, int F, bool noise = false) {
+// park: the pair runs a parking path kernel (park_pair): DPI_PARK_MAX_BLOCKS rows of PARK_ROW floats,
+// one per path block of a call, in which a terminal-first block keeps its terminal sums across the
+// MLP (dpi_device.h paths_body).  A constant, so the workspace stays affine in n and M; a call with
+// more path blocks than rows leaves it unused and runs every block terminal-last.
+static bool park_pair(dpi_problem p, dpi_net net);
+static WsLayout ws_layout(dpi_net net, int n, int M, int F, bool noise = false, bool park = false) {
   WsLayout w;
   // bx rows: the specialised image's H, or the general one's width cap (the wider of the two)
   const int H = (net && net->d.kind == 1) ? std::max(net->spec ? net->d.H : 0, net->gen ? net->g.H : 0) : 0;
@@ -1479,6 +1485,14 @@ static WsLayout ws_layout(dpi_net net, int n, int M, int F, bool noise = false) 
   if (net && net->d.kind == 1 && net->gen && !net->head) {
     w.stash = al256(w.total);
     w.total = w.stash + al256((size_t)gen_slots(net->g.H) * gen_slot_floats(net->g.L, net->g.ht) * 4);
+  }
+  // the park: the last region again, so every other offset stays where it was
+  w.park = w.total;
+  w.park_rows = 0;
+  if (park) {
+    w.park_rows = (size_t)DPI_PARK_MAX_BLOCKS;
+    w.park = al256(w.total);
+    w.total = w.park + w.park_rows * PARK_ROW * 4;
   }
   return w;
 }
@@ -1719,13 +1733,13 @@ static PisRows pis_chain(const NetPisDev& pd, float* rows, int R, hipStream_t st
 
 extern "C" size_t dpi_workspace_bytes(dpi_problem p, dpi_net net, int n, int M) {
   if (!p || n < 0 || M < 0) return 0;
-  return ws_layout(net, n, M, 1 + p->e.nx).total;
+  return ws_layout(net, n, M, 1 + p->e.nx, false, park_pair(p, net)).total;
 }
 // + the staged noise sums of a GBM MLP net's prepared calls (the last region of the layout, so a
 // plain call's offsets are the same)
 extern "C" size_t dpi_workspace_bytes_prepared(dpi_problem p, dpi_net net, int n, int M) {
   if (!p || n < 0 || M < 0) return 0;
-  return ws_layout(net, n, M, 1 + p->e.nx, gbm_noise_prep(p, net)).total;
+  return ws_layout(net, n, M, 1 + p->e.nx, gbm_noise_prep(p, net), park_pair(p, net)).total;
 }
 
 // the counters of draws 1-3 (k_sample_points, k_baseline's in-block sampling)
@@ -1781,6 +1795,16 @@ extern "C" int dpi_sample_points_t(dpi_problem p, int n, uint64_t seed, uint32_t
 // other MLP net within the general family's caps runs that (it holds the general image then).
 static bool runs_general(const dpi_problem_s* p, const dpi_net_s* net) {
   return net->d.kind == 1 && net->gen && !(net->spec && spec_shape(p->e.kind, net->d.H, net->d.L));
+}
+// The pairs whose workspace holds the park (dpi_device.h paths_body PARK): first-order Cha / OU labels
+// at nx <= 128 of any MLP net.  By problem and network kind only, not by the kernel family or instance
+// that ends up running: the workspace size does not move with the precision mode, ESTIMATE_DELTA_T or
+// the net's widths (a caller may set the first two after sizing it), and the workspaces of the
+// specialised and the general family keep differing by the general family's stash alone.  The kernels
+// that park are the fp16-split specialised instances (not OU 4 x 128 ELU, PARK_SPILLS); every other
+// launch leaves the region unused.
+static bool park_pair(dpi_problem p, dpi_net net) {
+  return p && net && net->d.kind == 1 && p->e.kind != DPI_EQ_GBM && p->e.nx <= NXP_MAX;
 }
 // The general family's refusals, each naming its cap.  td: the call uses the TD estimators.
 static int general_refusal(const dpi_problem_s* p, const dpi_net_s* net, bool td, bool hess) {
@@ -2094,7 +2118,11 @@ int dpi_point_baseline(dpi_problem p, dpi_net net, const float* tx, int n, void*
 // (read per call, so one process can compare both).
 static bool fused_reduce_on() { return env_int("DPI_FUSED_REDUCE", 1) != 0; }
 
-// k_paths phase order policy (see the kernel); DPI_ORDER overrides for ablations.
+// k_paths phase order policy (see the kernel, "Phase order"), read per call; DPI_ORDER overrides for
+// ablations.  0: the default — all terminal-first (split instances: parked, as 5).  1: the two
+// workgroups of a CU in opposite orders by workgroup slot, 2 / 3: by block index, 4: all
+// terminal-last, 5: all terminal-first.  Split launches without a park (more than
+// DPI_PARK_MAX_BLOCKS path blocks, OU 4 x 128 ELU) run terminal-last whatever it says.
 static int path_order() { return env_int("DPI_ORDER", 0); }
 
 static size_t hess_extra(int n, int M, int nx, size_t* moff);
@@ -2129,7 +2157,7 @@ static int label_args(dpi_problem p, dpi_net net, const float* tx, int n, int M,
                                  ": at most DPI_PATHS_PER_CALL_MAX paths per call");
   // the noise staging region only for dpi_label_prepare and the DPI_PREPARED call it feeds
   const bool noise = prepared && gbm_noise_prep(p, net);
-  *w = ws_layout(net, n, M, F, noise);
+  *w = ws_layout(net, n, M, F, noise, park_pair(p, net));
   if (hess) {
     size_t moff;
     if (ws_bytes < al256(w->total) + hess_extra(n, M, p->e.nx, &moff))
@@ -2162,6 +2190,9 @@ static int label_args(dpi_problem p, dpi_net net, const float* tx, int n, int M,
   a.point_base = point_base;
   a.order = path_order();
   a.split = mlp_split(net) ? 1 : 0;
+  // the split specialised instances' park, when it holds a row for every path block of this call
+  if (a.split && !runs_general(p, net) && w->park_rows && (size_t)n * nbp <= w->park_rows)
+    a.park = (float*)(b + w->park);
   a.td_dt = p->td_dt;
   return 0;
 }
@@ -2263,7 +2294,7 @@ int dpi_sample_with_gradients(dpi_problem p, dpi_net net, int n, int M, int K, u
   if (n == 0) return 0;
   if (!tx || !y || !moments) return fail(DPI_ERR_ARG, "sample_with_gradients: null tx, y or moments");
   const int F = 1 + p->e.nx;
-  const WsLayout w = ws_layout(net, n, M, F);
+  const WsLayout w = ws_layout(net, n, M, F, false, park_pair(p, net));
   if (!ws || ws_bytes < w.total) return fail(DPI_ERR_WORKSPACE, "workspace too small");
   if (net->d.kind == 2) {
     if ((rc = dpi_sample_points_t(p, n, seed, epoch, point_base, eps, t_factors, tx, stream))) return rc;
@@ -2485,7 +2516,7 @@ int dpi_generate_with_gradients(dpi_problem p, dpi_net net, const float* tx, int
   if (n < 0 || M < 1 || K < 1) return fail(DPI_ERR_ARG, "generate_with_gradients: bad arguments (n >= 0, M, K >= 1)");
   if (n == 0) return 0;
   const int F = 1 + p->e.nx;
-  const WsLayout w = ws_layout(net, n, M, F);
+  const WsLayout w = ws_layout(net, n, M, F, false, park_pair(p, net));
   if (!ws || ws_bytes < w.total) return fail(DPI_ERR_WORKSPACE, "workspace too small");
   if (!moments) return fail(DPI_ERR_ARG, "generate_with_gradients: moments buffer (n*2*(1+nx) floats) required");
   if ((rc = dpi_point_baseline(p, net, tx, n, ws, ws_bytes, stream))) return rc;
@@ -2524,8 +2555,9 @@ static int hess_moments_impl(dpi_problem p, dpi_net net, const float* tx, int n,
                              float* hsum, void* ws, size_t ws_bytes, void* stream, float* y, float bound) {
   // The shared validation and PathArgs fill; a.split selects the fp16-split tangent sweeps
   // (mlp_hdiag_split) unless DPI_GEMM_F32.  label_args also sets a.order (DPI_ORDER) and a.td_dt,
-  // which the Hessian-label launch ignores: k_paths reads a.order only in its non-GBM, non-split
-  // instances and a.td_dt only under TD, and the Hessian instances are GBM and non-TD.
+  // which the Hessian-label launch ignores: k_paths reads a.order only in its non-GBM instances (the
+  // split ones among them where the call has a park, a.park) and a.td_dt only under TD, and the
+  // Hessian instances are GBM and non-TD.
   WsLayout w;
   PathArgs a;
   int rc = label_args(p, net, tx, n, M, K, seed, epoch, point_base, m_begin, m_end, flags, true, moments, ws, ws_bytes,

@@ -245,7 +245,16 @@ int dpi_build_id(char* buf, size_t len);
 int dpi_launch_timer_arm(int slot);
 int dpi_launch_timer_ms(int slot, float* ms);
 
-/* Device workspace a dpi_* call on (p, net, n points, M paths) needs. */
+/* Device workspace a dpi_* call on (p, net, n points, M paths) needs.
+ * Cha / OU problems (nx <= 128) with an MLP net of any shape add the park as the last region (the
+ * specialised fp16-split path kernels use it; not OU 4 x 128 ELU): DPI_PARK_MAX_BLOCKS rows of
+ * 32 KB (4 waves x 8 dim-blocks x 64 paths x 4 floats), 64 MB whatever n and M, one row per 64-path
+ * block of a label call.  A path block that runs its terminal rollout first keeps the terminal sums
+ * there across its MLP phase, which lets its two rollouts run back to back (DESIGN.md §2.2 has the
+ * measurements).  A call with more than DPI_PARK_MAX_BLOCKS path blocks (n * ceil(paths / 64)) does
+ * not use the park and runs the order it ran before.  2,048 blocks are four rounds of the 512
+ * workgroups an MI355X holds. */
+#define DPI_PARK_MAX_BLOCKS 2048
 size_t dpi_workspace_bytes(dpi_problem p, dpi_net net, int n, int M);
 
 /* Workspace of dpi_label_prepare and of the DPI_PREPARED dpi_label_moments call it feeds: for a GBM

@@ -24,7 +24,7 @@ UNITS = ["dpi_kernels.hip", "dpi_paths_cha.hip", "dpi_paths_ou.hip", "dpi_paths_
          "dpi_paths_fb_cha.hip", "dpi_paths_fb_ou.hip", "dpi_paths_wide_cha.hip", "dpi_paths_wide_ou.hip",
          "dpi_paths_wide_cha_tanh.hip", "dpi_paths_wide_ou_tanh.hip", "dpi_paths_wide_gbm.hip",
          "dpi_paths_wide_gbm_tanh.hip", "dpi_paths_gen_cha.hip", "dpi_paths_gen_ou.hip", "dpi_paths_gen_cha_tanh.hip",
-         "dpi_paths_gen_ou_tanh.hip", "dpi_paths_head_cha_128.hip", "dpi_paths_head_cha_256.hip",
+         "dpi_paths_gen_ou_tanh.hip", "dpi_paths_gen_gbm.hip", "dpi_paths_gen_gbm_tanh.hip", "dpi_paths_head_cha_128.hip", "dpi_paths_head_cha_256.hip",
          "dpi_paths_head_ou_128.hip", "dpi_paths_head_ou_256.hip", "dpi_paths_head_cha_128_tanh.hip",
          "dpi_paths_head_cha_256_tanh.hip", "dpi_paths_head_ou_128_tanh.hip", "dpi_paths_head_ou_256_tanh.hip",
          "dpi_paths_head_base_cha.hip", "dpi_paths_head_base_ou.hip", "dpi_paths_term_cha.hip", "dpi_paths_term_ou.hip",

@@ -1819,6 +1819,7 @@ __global__ __launch_bounds__(NTHB) void k_baseline_gbm(EqDev e, NetDev net, cons
 
 }  // namespace dpi
 #include "dpi_general.h"
+#include "dpi_general_gbm.h"
 namespace dpi {
 
 struct PathArgs {
@@ -2272,14 +2273,17 @@ __device__ __forceinline__ void paths_body(const EqDev& e, const NET& net, const
   constexpr bool HEAD = std::is_same_v<NET, NetGenHead>;
   constexpr bool GEN = std::is_same_v<NET, NetGen> || HEAD;
   static_assert(!TERMA || GEN, "the terminal ansatz: general-family nets");
-  static_assert(!GEN || (KIND != DPI_EQ_GBM && !ZERO && !SPLIT && !HESS && !TD && !FBT && NXW == NXP_MAX),
-                "the general family: first-order Cha / OU labels, exact fp32, nx <= 128");
+  static_assert(!GEN || (!ZERO && !SPLIT && !HESS && !TD && !FBT && NXW == NXP_MAX),
+                "the general family: first-order labels, exact fp32, nx <= 128");
+  static_assert(!(GEN && KIND == DPI_EQ_GBM) || (!HEAD && !TERMA && H == GG_H),
+                "the general family on GBM (dpi_general_gbm.h): value nets of widths <= 64");
   static_assert(!HESS || KIND == DPI_EQ_GBM, "Hessian labels: GBM (SimpleDiffusionEquationWithHessian) only");
   static_assert(!(HESS && TD), "the Hessian-label estimators have no TD variant (data.py:1220-1223)");
   static_assert(NXW == NXP_MAX || (!HESS && !TD && !FBT && NXW % 128 == 0 && NXW <= NXW_MAX),
                 "wide instances: first-order labels, no TD, no fused baseline");
   static_assert(!(KIND == DPI_EQ_GBM && NXW > NXP_MAX) || L <= 3, "wide GBM instances: the hidden weights of L <= 3");
-  using SH = std::conditional_t<GEN, LdsGen<H>, std::conditional_t<KIND == DPI_EQ_GBM, LdsGbm<H, NXW>, LdsT<NXW>>>;
+  using SH = std::conditional_t<GEN, std::conditional_t<KIND == DPI_EQ_GBM, LdsGbmGen, LdsGen<H>>,
+                                std::conditional_t<KIND == DPI_EQ_GBM, LdsGbm<H, NXW>, LdsT<NXW>>>;
   constexpr int NBW = NXW / 16;  // dim-blocks of 4 per wave (4 waves)
   __shared__ SH sh;
   constexpr bool GBM = KIND == DPI_EQ_GBM;
@@ -2416,7 +2420,12 @@ __device__ __forceinline__ void paths_body(const EqDev& e, const NET& net, const
     }
   }
   if constexpr (GBM) {
-    if (!ZERO) {  // all weights resident for the tangent sweep (wide instances: W1x from L2)
+    if constexpr (GEN) {  // W1x resident; the hidden layers are staged by mlp_hdiag_gen
+      for (int idx = tid; idx < H * nxp; idx += NTH) {
+        const int h = idx / nxp, d = idx - h * nxp;
+        sh.W1x[h * SH::WXS + d] = net.W1x[idx];
+      }
+    } else if (!ZERO) {  // all weights resident for the tangent sweep (wide instances: W1x from L2)
       [[maybe_unused]] constexpr int WXS = SH::WXS;
       constexpr int WHS = SH::WHS;
       if constexpr (SH::W1X_LDS)
@@ -2589,7 +2598,9 @@ __device__ __forceinline__ void paths_body(const EqDev& e, const NET& net, const
       float s1 = 0.f, s2 = 0.f;
       if constexpr (!ZERO) {
         if (INTG) {
-          if constexpr (SPLIT)
+          if constexpr (GEN)
+            mlp_hdiag_gen<ACT>(e, net, sh, stash, s1, s2);
+          else if constexpr (SPLIT)
             mlp_hdiag_split<H, L, ACT>(e, net, sh, nxp / 16, s1, s2);
           else
             mlp_hdiag<H, L, ACT>(e, net, sh, nxp / 16, s1, s2);
@@ -2652,7 +2663,9 @@ __device__ __forceinline__ void paths_body(const EqDev& e, const NET& net, const
   if constexpr (TD) {
     tlast = false;  // the terminal MLP needs the noise tile before the integral rollout
   } else if constexpr (GEN) {
-    tlast = true;  // the terminal sums are not live across the MLP (its two layers of registers)
+    // the terminal sums are not live across the MLP (its two layers of registers); GBM: terminal-first as
+    // its specialised instances, whose integrand reads the fst that terminal_finish publishes
+    tlast = !GBM;
   } else if constexpr (SPLIT && !GBM) {
     tlast = true;  // the terminal sums are not live across the MLP (no spills)
     if constexpr (PARK) {
@@ -2688,7 +2701,7 @@ __device__ __forceinline__ void paths_body(const EqDev& e, const NET& net, const
     __syncthreads();
     float u = 0.f;
     if constexpr (!ZERO) {
-      if constexpr (GBM) {
+      if constexpr (GBM && !GEN) {
         u = mlp_value_res<H, L, ACT>(net, sh, nxp / 16);
       } else if constexpr (!GEN) {
         float gs, gA, gB;
@@ -2983,6 +2996,15 @@ template <int KIND, int HCAP, int ACT>
 __global__ __launch_bounds__(256, (gen_wgs(HCAP))) void k_paths_head(EqDev e, NetGenHead net, PathArgs a) {
   paths_body<KIND, HCAP, GEN_LMAX, false, false, false, false, ACT, false, NXP_MAX, NetGenHead>(e, net, a, FusedBase{},
                                                                                                  blockIdx.x, nullptr);
+}
+// The general family's GBM path launch (dpi_general_gbm.h): launched in block ranges as k_paths_gen is, at
+// most GG_SLOTS workgroups each, one per CU (its sweep holds 4 directions x 2 layers of tangents).
+template <int ACT>
+__global__ __launch_bounds__(256, 1) void k_paths_gbm_gen(EqDev e, NetGen net, PathArgs a, floatx4* stash,
+                                                         unsigned block0) {
+  floatx4* const slot = stash + (size_t)blockIdx.x * gg_slot_vec4(net.L, net.ht);
+  paths_body<DPI_EQ_GBM, GG_H, GEN_LMAX, false, false, false, false, ACT, false, NXP_MAX, NetGen>(
+      e, net, a, FusedBase{}, block0 + blockIdx.x, slot);
 }
 // The terminal-enforcing forms of both (dpi_general.h, TERMA): launched as their plain twins are.
 template <int KIND, int HCAP, int ACT>

@@ -192,6 +192,30 @@ bool dispatch_gen(const dpi_problem_s* p, const dpi_net_s* net, const Launch& q)
   return true;
 }
 
+// The general family's GBM units (dpi_general_gbm.h; rows gen_gbm, gen_gbm_tanh): k_paths_gbm_gen, and in
+// the ELU unit the activation-generic k_baseline_gbm_gen.
+template <int ACT>
+bool dispatch_gen_gbm(const dpi_problem_s* p, const dpi_net_s* net, const Launch& q) {
+  const NetGen& g = net->g;
+  if (g.H != 128 || g.ht > GG_H / 16) return false;  // the width-128 image, widths <= 64
+  if (q.baseline) {
+    if constexpr (ACT == DPI_ACT_ELU) {
+      hipLaunchKernelGGL((k_baseline_gbm_gen<GG_H>), dim3(q.n), dim3(NTHB), 0, q.st, p->e, g, q.tx, q.n, q.gx, q.fb, q.bx, q.hb,
+                         q.smp, q.tickets);
+      return true;
+    }
+    return false;
+  }
+  if (q.hess || q.td || q.fbase || !q.stash || p->e.nx > NXP_MAX) return false;
+  const unsigned nblocks = (unsigned)q.nblocks, slots = (unsigned)GG_SLOTS;
+  for (unsigned b0 = 0; b0 < nblocks; b0 += slots) {
+    const unsigned grid = std::min(nblocks - b0, slots);
+    hipEvent_t t0 = b0 ? nullptr : q.t0, t1 = b0 ? nullptr : q.t1;
+    hipExtLaunchKernelGGL((k_paths_gbm_gen<ACT>), dim3(grid), dim3(NTH), 0, q.st, t0, t1, 0, p->e, g, *q.a, q.stash, b0);
+  }
+  return true;
+}
+
 // The head units (HEADV rows of DPI_UNITS; dpi_general.h NetGenHead): HEADV = 128 / 256 holds
 // k_paths_head at that width cap, one launch over all blocks; HEADV = HEAD_BASE the activation-generic
 // k_baseline_head.
@@ -222,8 +246,11 @@ template <int KIND, bool TDV = false, int ACT = DPI_ACT_ELU, bool FBV = false, i
           int HEADV = 0, bool TERMV = false>
 bool dpi_dispatch(const dpi_problem_s* p, const dpi_net_s* net, const Launch& q) {
   if constexpr (GENV) {
-    static_assert(KIND != DPI_EQ_GBM && !TDV && !FBV && NXW == NXP_MAX, "the general family: first-order Cha / OU");
-    if constexpr (HEADV != 0)
+    static_assert(!TDV && !FBV && NXW == NXP_MAX, "the general family: first-order labels, nx <= 128");
+    static_assert(KIND != DPI_EQ_GBM || (HEADV == 0 && !TERMV), "GBM: value nets only");
+    if constexpr (KIND == DPI_EQ_GBM)
+      return dispatch_gen_gbm<ACT>(p, net, q);
+    else if constexpr (HEADV != 0)
       return dispatch_head<KIND, ACT, HEADV, TERMV>(p, net, q);
     else
       return dispatch_gen<KIND, ACT, TERMV>(p, net, q);
@@ -294,6 +321,8 @@ bool dpi_dispatch(const dpi_problem_s* p, const dpi_net_s* net, const Launch& q)
   X(gen_ou, DPI_EQ_OU, false, DPI_ACT_ELU, false, NXP_MAX, true, 0, false) \
   X(gen_cha_tanh, DPI_EQ_CHA, false, DPI_ACT_TANH, false, NXP_MAX, true, 0, false) \
   X(gen_ou_tanh, DPI_EQ_OU, false, DPI_ACT_TANH, false, NXP_MAX, true, 0, false) \
+  X(gen_gbm, DPI_EQ_GBM, false, DPI_ACT_ELU, false, NXP_MAX, true, 0, false) \
+  X(gen_gbm_tanh, DPI_EQ_GBM, false, DPI_ACT_TANH, false, NXP_MAX, true, 0, false) \
   X(head_cha_128, DPI_EQ_CHA, false, DPI_ACT_ELU, false, NXP_MAX, true, 128, false) \
   X(head_cha_256, DPI_EQ_CHA, false, DPI_ACT_ELU, false, NXP_MAX, true, 256, false) \
   X(head_ou_128, DPI_EQ_OU, false, DPI_ACT_ELU, false, NXP_MAX, true, 128, false) \

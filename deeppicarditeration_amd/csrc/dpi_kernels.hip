@@ -1834,9 +1834,17 @@ static int general_refusal(const dpi_problem_s* p, const dpi_net_s* net, bool td
   }
   const char* pre = "this network has no specialised kernel instance and the general MLP family (up to 8 hidden "
                     "layers of width 256) ";
-  if (p->e.kind == DPI_EQ_GBM)
-    return fail(DPI_ERR_UNSUPPORTED, std::string(pre) + "serves Cha and OU problems only: GBM nets need one of its compiled "
-                                                        "shapes (widths <= 64, at most 3 hidden layers)");
+  if (p->e.kind == DPI_EQ_GBM) {  // dpi_general_gbm.h: the width-128 image with at most 4 tiles in use
+    if (net->g.H != 128 || net->g.ht > GG_H / 16 || net->g.L > GEN_LMAX)
+      return fail(DPI_ERR_UNSUPPORTED, std::string(pre) + "serves GBM problems for hidden widths <= 64 only (up to 8 hidden "
+                                                          "layers): GBM keeps W1x and the tangents of every layer on chip");
+    const char* pg = "this GBM network has no specialised kernel instance and the general MLP family on GBM (up to 8 hidden "
+                     "layers of width 64) ";
+    if (hess) return fail(DPI_ERR_UNSUPPORTED, std::string(pg) + "has no Hessian labels (nor SUPERVISE_HESSIAN)");
+    if (p->e.nx > NXP_MAX) return fail(DPI_ERR_UNSUPPORTED, std::string(pg) + "is compiled for nx <= 128 (NXP_MAX)");
+    if (td) return fail(DPI_ERR_UNSUPPORTED, std::string(pg) + "has no TD estimators (ESTIMATE_DELTA_T > 0)");
+    return 0;
+  }
   if (hess) return fail(DPI_ERR_UNSUPPORTED, std::string(pre) + "has no Hessian labels");
   if (p->e.nx > NXP_MAX)
     return fail(DPI_ERR_UNSUPPORTED, std::string(pre) + "is compiled for nx <= 128 (NXP_MAX)");
@@ -1844,6 +1852,17 @@ static int general_refusal(const dpi_problem_s* p, const dpi_net_s* net, bool td
     return fail(DPI_ERR_UNSUPPORTED, std::string(pre) + "has no TD estimators (ESTIMATE_DELTA_T > 0): those need at most "
                                                         "4 hidden layers of width 128");
   return 0;
+}
+
+// A GBM MLP pair that neither family serves: some hidden layer is wider than 64 (a net of 2-4 layers up to
+// 128 wide holds the specialised image only, so runs_general does not see it).
+static bool gbm_too_wide(const dpi_problem_s* p, const dpi_net_s* net) {
+  return p->e.kind == DPI_EQ_GBM && net->d.kind == 1 && !runs_general(p, net) &&
+         !(net->spec && spec_shape(DPI_EQ_GBM, net->d.H, net->d.L));
+}
+static int gbm_too_wide_refusal() {
+  return fail(DPI_ERR_UNSUPPORTED, "GBM networks need every hidden layer <= 64 wide (up to 8 hidden layers): GBM keeps W1x "
+                                   "and the tangents of every layer on chip");
 }
 
 static bool dispatch_any(const dpi_problem_s* p, const dpi_net_s* net, const Launch& q) {
@@ -1915,6 +1934,7 @@ static int check_pair(dpi_problem p, dpi_net net) {
   if (runs_general(p, net)) {
     if (int rc = general_refusal(p, net, p->td_dt > 0.f, false)) return rc;
   }
+  if (gbm_too_wide(p, net)) return gbm_too_wide_refusal();
   if (net->term && net->term_T != p->e.T)
     return fail(DPI_ERR_ARG, "the terminal-enforcing net was built for another T than the problem's");
   return 0;
@@ -1930,6 +1950,7 @@ int dpi_pair_family(dpi_problem p, dpi_net net, int td, int* family) {
     *family = DPI_FAMILY_GENERAL;
     return 0;
   }
+  if (gbm_too_wide(p, net)) return gbm_too_wide_refusal();
   if (!spec_shape(p->e.kind, net->d.H, net->d.L))
     return fail(DPI_ERR_UNSUPPORTED, "pair_family: unsupported equation/network shape");
   return 0;
@@ -2625,7 +2646,8 @@ int dpi_generate_with_gradients_and_hessians(dpi_problem p, dpi_net net, const f
                                              float* y, void* ws, size_t ws_bytes, void* stream) {
   int rc = check_pair(p, net);
   if (rc) return rc;
-  if (net->head || net->term) return general_refusal(p, net, false, true);  // no Hessian labels
+  if (net->head || net->term || (p->e.kind == DPI_EQ_GBM && runs_general(p, net)))
+    return general_refusal(p, net, false, true);  // no Hessian labels
   if (n < 0 || (!y && n) || M < 1 || M > 1024 * P)
     return fail(DPI_ERR_ARG, "generate_with_gradients_and_hessians: bad arguments (1 <= M <= 65536)");
   if (n == 0) return 0;

@@ -129,9 +129,12 @@ int dpi_net_create_zero(dpi_net* out);
  * are zero-padded to a compiled width class H in {16, 32, 64, 128, 256} that holds the widest one.
  * First-order Cha / OU labels (nx <= 128, no TD): every such net — a specialised kernel instance
  * where (H, n_hidden) has one ((128, 2-4), (64, 2-3), (32, 2), (16, 1-3)), the general MLP family
- * (exact fp32, run-time layer count) for every other pair.  GBM, the TD estimators, the Hessian
- * labels and nx > 128 have the specialised instances only (GBM: (64, 2-3), (32, 2-3), (16, 1-3));
- * any other net is refused at the label call with DPI_ERR_UNSUPPORTED (dpi_pair_family tells).
+ * (exact fp32, run-time layer count) for every other pair.  First-order GBM labels (SDGD or the exact
+ * diagonal, nx <= 128, no TD): every such net whose layers are all <= 64 wide — the specialised
+ * instances (64, 2-3), (32, 2-3), (16, 1-3), the general family's GBM kernels (exact fp32) for every
+ * other pair: (64, 1), (32, 1), 4-8 layers.  A GBM net with a layer wider than 64, and the TD
+ * estimators, the Hessian labels and nx > 128 of a net without a specialised instance, are refused
+ * at the label call with DPI_ERR_UNSUPPORTED (dpi_pair_family tells).
  * act: the activation of every hidden layer, DPI_ACT_ELU (torch.nn.ELU, alpha = 1) or DPI_ACT_TANH
  * (torch.nn.Tanh, the reference's default NETWORK.ACTIVATIONS, picard/config.py:61). */
 int dpi_net_create_mlp(int n_in, int n_hidden, const int* widths, int act, const float* params,
@@ -170,7 +173,8 @@ int dpi_net_create_mlp_terminal(int n_in, int n_hidden, const int* widths, int a
  * DPI_FAMILY_SPECIALISED (also for zero and PISGradNet nets) or DPI_FAMILY_GENERAL, the general MLP
  * family, which is fp32 only: dpi_set_gemm_precision / dpi_net_set_precision select nothing for it.
  * td != 0: for the TD estimators (ESTIMATE_DELTA_T > 0).  DPI_ERR_UNSUPPORTED, with the reason in
- * dpi_last_error, for a pair the label calls would refuse. */
+ * dpi_last_error, for a pair the label calls would refuse: the general family has no TD estimators and
+ * ends at nx = 128, and with GBM at hidden widths of 64 (up to 8 hidden layers). */
 #define DPI_FAMILY_SPECIALISED 0
 #define DPI_FAMILY_GENERAL 1
 int dpi_pair_family(dpi_problem p, dpi_net net, int td, int* family);

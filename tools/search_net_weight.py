@@ -6,7 +6,11 @@ the GPU tests gate at the device's fp32 points, the CPU test at the oracle's fp6
 whose shares lie deepest inside the band (largest min over blocks of min(log(s / 0.05), log(0.95 / s))),
 as a line of the SCALES literal.  No device is needed.
 
-    python tools/search_net_weight.py [-j PROCESSES] [--seeds 17,18,...] [substring of the net ids to search]"""
+    python tools/search_net_weight.py [-j PROCESSES] [--seeds 17,18,...] [--cases MODULE] [substring of the net ids]
+
+--cases MODULE: another case module under tests/ with net_weight_cases' interface (CASES, net_id, equations,
+network, oracle_kw, N, SEED, EPOCH), for instance gbm_deep_cases."""
+import importlib
 import math
 import os
 import sys
@@ -19,6 +23,11 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 
 LO, HI, FLOOR = 0.052, 0.94, 1.1e-3
 SEEDS = [17]
+CASES = ["net_weight_cases"]
+
+
+def cases_module():
+    return importlib.import_module(CASES[0])
 
 
 def search(c):
@@ -34,8 +43,8 @@ def search_seed(c, seed):
     import torch
 
     import net_weight as NW
-    import net_weight_cases as T
     from oracle import dpi_oracle as O
+    T = cases_module()
     torch.set_num_threads(1)
     eq, oeq = T.equations(c)
     tx = O.sample_points(oeq, T.N, T.SEED, T.EPOCH, 0)
@@ -68,19 +77,26 @@ def search_seed(c, seed):
     return T.net_id(c), best
 
 
+def _init(seeds, cases):  # the workers' copies of the options (a spawned worker re-imports this module)
+    SEEDS[:] = seeds
+    CASES[:] = cases
+
+
 def main():
-    import net_weight_cases as T
     args = sys.argv[1:]
     jobs = int(args[args.index("-j") + 1]) if "-j" in args else 8
     if "--seeds" in args:  # net seeds to try in turn where 17 gives no candidate
         SEEDS[:] = [int(x) for x in args[args.index("--seeds") + 1].split(",")]
-    flags = ("-j", "--seeds")
+    if "--cases" in args:
+        CASES[:] = [args[args.index("--cases") + 1]]
+    T = cases_module()
+    flags = ("-j", "--seeds", "--cases")
     pats = [a for i, a in enumerate(args) if a not in flags and (i == 0 or args[i - 1] not in flags)]
     nets = {}
     for c in T.CASES:
         if not pats or any(p in T.net_id(c) + "$" for p in pats):  # 'nx7$' ends an id
             nets.setdefault(T.net_id(c), c)
-    with Pool(jobs) as pool:
+    with Pool(jobs, _init, (list(SEEDS), list(CASES))) as pool:
         for nid, best, seed in pool.imap(search, list(nets.values())):
             if best is None:
                 print(f"    # {nid!r}: NO CANDIDATE PASSES", flush=True)

@@ -1,7 +1,8 @@
 """Build libdpi_hip.so in-tree for gfx950 (hipcc cross-compiles without a GPU).
 
-The translation units of `UNITS` (the C-ABI / PIS / reduce TU, and one `dpi_paths_*.hip` per row of the
-unit table in `csrc/dpi_dispatch.h`) compile in parallel to objects, then link into one
+The translation units of `UNITS` (the C-ABI / PIS / reduce TU, the network-handle TU, and one
+`dpi_paths_*.hip` per row of the unit table in `csrc/dpi_dispatch.h`) compile in parallel, at most
+`MAX_JOBS` at once, to objects, then link into one
 shared library together with a generated one-function unit, `dpi_build_id()`, that returns the
 SHA-256 of the sources and flags (`source_hash`).  A build is current when the library itself
 embeds the tree's hash (not by mtime, and not by a side file that a checkout could leave behind
@@ -18,7 +19,7 @@ from pathlib import Path
 ROOT = Path(__file__).resolve().parent
 REPO = ROOT.parent
 CSRC = ROOT / "csrc"
-UNITS = ["dpi_kernels.hip", "dpi_paths_cha.hip", "dpi_paths_ou.hip", "dpi_paths_gbm.hip", "dpi_paths_td_cha.hip",
+UNITS = ["dpi_kernels.hip", "dpi_net.hip", "dpi_paths_cha.hip", "dpi_paths_ou.hip", "dpi_paths_gbm.hip", "dpi_paths_td_cha.hip",
          "dpi_paths_td_ou.hip", "dpi_paths_td_gbm.hip", "dpi_paths_cha_tanh.hip", "dpi_paths_ou_tanh.hip",
          "dpi_paths_gbm_tanh.hip", "dpi_paths_td_cha_tanh.hip", "dpi_paths_td_ou_tanh.hip", "dpi_paths_td_gbm_tanh.hip",
          "dpi_paths_fb_cha.hip", "dpi_paths_fb_ou.hip", "dpi_paths_wide_cha.hip", "dpi_paths_wide_ou.hip",
@@ -37,6 +38,7 @@ OBJ = ROOT / "build"
 OUT = ROOT / "libdpi_hip.so"
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", f"-I{REPO / 'include'}"]
+MAX_JOBS = 16  # compilers at once: one per stale unit oversubscribes a machine that grants fewer CPUs
 
 
 def sources():
@@ -110,7 +112,7 @@ def build(force=False, verbose=True):
 
     bid = source_hash()  # before compiling: a source edited during the build leaves the result stale
     todo = [u for u in UNITS if stale(u)]
-    with ThreadPoolExecutor(max_workers=max(1, len(todo))) as ex:
+    with ThreadPoolExecutor(max_workers=max(1, min(MAX_JOBS, len(todo)))) as ex:
         list(ex.map(compile_unit, todo))
     objs = [OBJ / (Path(u).stem + ".o") for u in UNITS]
     objs.append(build_id_object(bid))

@@ -1,6 +1,7 @@
-// C-ABI of include/dpi.h (libdpi_hip.so): problem / network handles, the PISGradNet pipeline
-// host code, label moments, reduce and finalize kernels.  Device code: dpi_device.h; the per
-// equation k_paths instantiations: dpi_paths_{cha,ou,gbm}.hip.
+// C-ABI of include/dpi.h (libdpi_hip.so): problem handles, workspace layout, routing, the
+// PISGradNet pipeline host code, the label calls, reduce and finalize kernels.  The network handles
+// and their device images: dpi_net.hip, dpi_net_image.h.  Device code: dpi_device.h; the k_paths /
+// k_baseline instantiations: one dpi_paths_*.hip unit per row of dpi_dispatch.h's unit table.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -22,6 +23,7 @@
 #include "dpi_rng.h"
 
 #include "dpi_dispatch.h"
+#include "dpi_host.h"
 #include "dpi_pisnet.h"
 
 namespace dpi {
@@ -219,30 +221,6 @@ __global__ void k_finalize(const float* moments, const float* gx, int n, int F, 
 
 }  // namespace dpi
 
-static thread_local std::string g_err;
-
-static int fail(int code, const std::string& msg) {
-  g_err = msg;
-  return code;
-}
-#define HIPCHK(x)                                                                                    \
-  do {                                                                                               \
-    hipError_t _e = (x);                                                                             \
-    if (_e != hipSuccess) return fail(DPI_ERR_HIP, std::string(#x) + ": " + hipGetErrorString(_e)); \
-  } while (0)
-
-// The integer / real environment knobs: unset gives dflt, a set value is clamped
-// to [lo, hi].  A knob read once per process keeps the result in a function-local static; the ones
-// a test flips inside one process call these afresh.
-static int env_int(const char* name, int dflt, int lo = INT_MIN, int hi = INT_MAX) {
-  const char* e = std::getenv(name);
-  return e ? std::max(lo, std::min(hi, std::atoi(e))) : dflt;
-}
-static double env_real(const char* name, double dflt, double lo, double hi) {
-  const char* e = std::getenv(name);
-  return e ? std::max(lo, std::min(hi, std::atof(e))) : dflt;
-}
-
 template <typename T>
 static int upload(dpi_problem_s* p, const std::vector<T>& v, const T** out) {
   void* d = nullptr;
@@ -251,243 +229,6 @@ static int upload(dpi_problem_s* p, const std::vector<T>& v, const T** out) {
   p->dev.push_back(d);
   *out = reinterpret_cast<const T*>(d);
   return 0;
-}
-
-// The same fragment order for the split-storage GEMM (k_gemm_x3, dpi_gemm.h): x' = 2^s x with
-// max |x'| in [0.5, 1), hi = fp16(x'), lo = fp16(x' - hi) (unscaled).  *wscale = 2^-s.
-
-// Fragment-major copy of a packed split matrix (R rows of C words, R % 16 == 0, C % 32 == 0) for
-// k_pis_net: block (T, c) of 512 words = lane l's hi granule (row 16 T + l % 16, words
-// 32 c + 8 (l / 16) .. + 3) at 4 l, then its lo granule (the next 4 words) at 256 + 4 l.
-static size_t pack_frag_major(std::vector<float>& blob, size_t src, int R, int C) {
-  blob.resize((blob.size() + 31) & ~size_t(31), 0.f);
-  const size_t off = blob.size();
-  blob.resize(off + (size_t)R * C, 0.f);
-  const int nc = C / 32;
-  for (int T = 0; T < R / 16; ++T)
-    for (int c = 0; c < nc; ++c)
-      for (int h = 0; h < 2; ++h)
-        for (int l = 0; l < 64; ++l)
-          for (int j = 0; j < 4; ++j)
-            blob[off + (((size_t)T * nc + c) * 2 + h) * 256 + 4 * l + j] =
-                blob[src + (size_t)(16 * T + (l & 15)) * C + 32 * c + 8 * (l >> 4) + 4 * h + j];
-  return off;
-}
-
-template <class F>
-static size_t pack_split_x3(std::vector<float>& blob, int R, int C, F at, float* wscale) {
-  float mx = 0.f;
-  for (int r = 0; r < R; ++r)
-    for (int c = 0; c < C; ++c) mx = std::max(mx, std::fabs(at(r, c)));
-  int e = 0;
-  if (mx > 0.f) (void)std::frexp(mx, &e);  // mx = f 2^e, f in [0.5, 1)
-  const float sc = std::ldexp(1.0f, -e);
-  *wscale = std::ldexp(1.0f, e);
-  const size_t off = blob.size();
-  blob.resize(off + (size_t)R * C, 0.f);
-  _Float16* dst = reinterpret_cast<_Float16*>(blob.data() + off);
-  for (int r = 0; r < R; ++r)
-    for (int u = 0; u < C / 32; ++u)
-      for (int q = 0; q < 4; ++q) {
-        _Float16* g = dst + ((size_t)r * C + 32 * u + 8 * q) * 2;  // 16 halves = 8 words
-        for (int j = 0; j < 8; ++j) {
-          const float x = at(r, 32 * u + 4 * q + (j & 3) + 16 * (j >> 2)) * sc;
-          const _Float16 h = (_Float16)x;
-          g[j] = h;
-          g[8 + j] = (_Float16)(x - (float)h);
-        }
-      }
-  return off;
-}
-
-// Append an R x C (C % 32 == 0) matrix in the fp16-split fragment order of mlp_tile_split:
-// row r, chunk u, lane group q: 8 hi halves then 8 lo halves of columns 32u + 4q + (j & 3) + 16 (j >> 2).
-// Returns the offset (in 4-byte words) into `blob`.
-template <class F>
-static size_t pack_split(std::vector<float>& blob, int R, int C, F at) {
-  const size_t off = blob.size();
-  blob.resize(off + (size_t)R * C, 0.f);
-  _Float16* dst = reinterpret_cast<_Float16*>(blob.data() + off);
-  for (int r = 0; r < R; ++r)
-    for (int u = 0; u < C / 32; ++u)
-      for (int q = 0; q < 4; ++q) {
-        _Float16* g = dst + ((size_t)r * C + 32 * u + 8 * q) * 2;  // 16 halves = 8 words
-        for (int j = 0; j < 8; ++j) {
-          const float x = at(r, 32 * u + 4 * q + (j & 3) + 16 * (j >> 2));
-          const _Float16 h = (_Float16)x;
-          g[j] = h;
-          g[8 + j] = (_Float16)((x - (float)h) * 2048.0f);
-        }
-      }
-  return off;
-}
-
-// ---------------------------------------------------------------- operand exponents (split storage)
-// A value stored split with an unscaled residual, hi = fp16(v), lo = fp16(v - hi) (the x3 convention
-// of k_gemm_x3 / k_pis_net / k_pis_time and of the GBM tangent sweep), keeps fp32's relative precision
-// only while lo is an fp16 normal (|v| >~ 2^-2); below that its error is absolute, ~2^-25.  A network
-// with small weights makes every activation (or cotangent, or tangent) of a layer small, and the
-// products that read them then lose precision that exact fp32 keeps (tools/probe_small.py "homog").
-// So every such operand is stored as 2^e v, e per operand and network, chosen on the host from a
-// calibration pass of the network itself (double precision, fixed synthetic inputs) so that the
-// operand's rms is ~4: per element fp32-class down to ~rms/16, 2^14 of headroom above the rms before
-// fp16 overflows (the range guard's case).  The consuming product folds 2^-e into its weight scale,
-// so the arithmetic is a power of two per operand — exact.
-static int x3_exponent(double sumsq, double count) {
-  if (!(count > 0) || !(sumsq > 0) || !std::isfinite(sumsq)) return 0;
-  const int e = 2 - (int)std::lround(0.5 * std::log2(sumsq / count));
-  return std::min(std::max(e, -40), 40);
-}
-// fixed-seed N(0, 1) calibration inputs (splitmix64 + Box-Muller; host only, not a label draw)
-struct CalNormal {
-  uint64_t s = 0x9E3779B97F4A7C15ull;
-  double u01() {
-    uint64_t z = (s += 0x9E3779B97F4A7C15ull);
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return ((double)((z ^ (z >> 31)) >> 11) + 0.5) * (1.0 / 9007199254740992.0);
-  }
-  double operator()() { return std::sqrt(-2.0 * std::log(u01())) * std::cos(6.283185307179586 * u01()); }
-};
-constexpr int CAL_ROWS = 16;
-static double cal_act(int act, double z) { return act == DPI_ACT_TANH ? std::tanh(z) : (z > 0 ? z : std::expm1(z)); }
-static double cal_dact(int act, double a) { return act == DPI_ACT_TANH ? 1.0 - a * a : (a > 0 ? 1.0 : a + 1.0); }
-// y = W x + b (W row-major (o, in)); b may be null
-static void cal_affine(const float* W, const float* b, int o, int in, const double* x, double* y) {
-  for (int r = 0; r < o; ++r) {
-    double a = b ? (double)b[r] : 0.0;
-    const float* w = W + (size_t)r * in;
-    for (int k = 0; k < in; ++k) a += (double)w[k] * x[k];
-    y[r] = a;
-  }
-}
-// y = W^T x (W row-major (o, in), x of length o)
-static void cal_affine_t(const float* W, int o, int in, const double* x, double* y) {
-  for (int k = 0; k < in; ++k) y[k] = 0.0;
-  for (int r = 0; r < o; ++r) {
-    const float* w = W + (size_t)r * in;
-    for (int k = 0; k < in; ++k) y[k] += (double)w[k] * x[r];
-  }
-}
-
-// PISGradNet's operand exponents: t_encoder's hidden layer (te) and output (temb), the operand of
-// smooth_net block j (sn[j]), nn_module's activations A_l (a[l]) and VJP cotangents D_l (d[l]).
-// Calibration rows: lambda evenly over (0, T), X ~ N(0, 4 I) (the OU/HJB state scale, x ~ N(0, (4 + t) I)).
-struct PisExps {
-  int te, temb, sn[4], a[4], d[4];
-};
-static PisExps pis_calibrate(int nx, int L, const int* hidden, double T, const float* phase, const float* coeff,
-                             const float* te0, const float* te0b, const float* te2, const float* te2b, const float* sn0,
-                             const float* sn0b, const float* const* snw, const float* const* snbw, int nsm,
-                             const float* const* nnw, const float* const* nnbw, const int* ins) {
-  const int C = PIS_CH;
-  double s_te = 0, s_temb = 0, s_sn[4] = {0, 0, 0, 0}, s_a[4] = {0, 0, 0, 0}, s_d[4] = {0, 0, 0, 0};
-  int hmax = C;
-  for (int l = 0; l < L; ++l) hmax = std::max(hmax, hidden[l]);
-  std::vector<double> e(2 * C), h(C), h2(C), in0(C + nx), A[4], D(hmax), D2(hmax);
-  for (int l = 0; l < L; ++l) A[l].assign(hidden[l], 0.0);
-  CalNormal nrm;
-  auto sq = [](const std::vector<double>& v, int n) {
-    double s = 0;
-    for (int k = 0; k < n; ++k) s += v[k] * v[k];
-    return s;
-  };
-  for (int r = 0; r < CAL_ROWS; ++r) {
-    const double lbd = T * (r + 0.5) / CAL_ROWS;
-    for (int j = 0; j < C; ++j) {
-      const double a = (double)coeff[j] * lbd + (double)phase[j];
-      e[j] = std::sin(a);
-      e[C + j] = std::cos(a);
-    }
-    cal_affine(te0, te0b, C, 2 * C, e.data(), h.data());
-    for (int k = 0; k < C; ++k) h[k] = cal_act(DPI_ACT_ELU, h[k]);
-    s_te += sq(h, C);
-    cal_affine(te2, te2b, C, C, h.data(), in0.data());
-    for (int k = 0; k < C; ++k) s_temb += in0[k] * in0[k];
-    cal_affine(sn0, sn0b, C, 2 * C, e.data(), h.data());
-    for (int j = 0; j < nsm; ++j) {
-      for (int k = 0; k < C; ++k) h[k] = cal_act(DPI_ACT_ELU, h[k]);
-      s_sn[j] += sq(h, C);
-      cal_affine(snw[j], snbw[j], C, C, h.data(), h2.data());
-      h.swap(h2);
-    }
-    for (int d = 0; d < nx; ++d) in0[C + d] = 2.0 * nrm();
-    const double* x = in0.data();
-    for (int l = 0; l < L; ++l) {
-      cal_affine(nnw[l], nnbw[l], hidden[l], ins[l], x, A[l].data());
-      for (int k = 0; k < hidden[l]; ++k) A[l][k] = cal_act(DPI_ACT_ELU, A[l][k]);
-      s_a[l] += sq(A[l], hidden[l]);
-      x = A[l].data();
-    }
-    // VJP with cotangent X on net_out: D_{L-1} = (nn_L^T X) elu'(A_{L-1}), D_{l-1} = (nn_l^T D_l) elu'(A_{l-1})
-    cal_affine_t(nnw[L], nx, ins[L], in0.data() + C, D.data());
-    for (int l = L - 1; l >= 0; --l) {
-      for (int k = 0; k < hidden[l]; ++k) D[k] *= cal_dact(DPI_ACT_ELU, A[l][k]);
-      s_d[l] += sq(D, hidden[l]);
-      if (l > 0) {
-        cal_affine_t(nnw[l], hidden[l], ins[l], D.data(), D2.data());
-        D.swap(D2);
-      }
-    }
-  }
-  PisExps x;
-  x.te = x3_exponent(s_te, (double)CAL_ROWS * C);
-  x.temb = x3_exponent(s_temb, (double)CAL_ROWS * C);
-  for (int j = 0; j < 4; ++j) x.sn[j] = j < nsm ? x3_exponent(s_sn[j], (double)CAL_ROWS * C) : 0;
-  for (int l = 0; l < 4; ++l) {
-    x.a[l] = l < L ? x3_exponent(s_a[l], (double)CAL_ROWS * hidden[l]) : 0;
-    x.d[l] = l < L ? x3_exponent(s_d[l], (double)CAL_ROWS * hidden[l]) : 0;
-  }
-  return x;
-}
-
-// The MLP tangent sweep's operand exponents (mlp_hdiag_split): activations a_l (the forward's B
-// operands of layers l + 1) and tangent operands act'(a_l) z_l, z_0 = W1x[:, d] over every direction d
-// (z_{l+1} = W_{l+1} (act'(a_l) z_l)).  Calibration rows: t evenly over (0, T), x ~ N(0, I).
-static void mlp_calibrate(int nx, int H, int L, int act, const float* W0, const float* b0, const float* const* W,
-                          const float* const* b, int* ea, int* eb) {
-  const int n_in = 1 + nx;
-  double sa[4] = {0, 0, 0, 0}, sb[4] = {0, 0, 0, 0};
-  std::vector<double> x(n_in), a[4], z((size_t)H * nx), zn((size_t)H * nx);
-  for (int l = 0; l < L; ++l) a[l].assign(H, 0.0);
-  CalNormal nrm;
-  for (int r = 0; r < CAL_ROWS; ++r) {
-    x[0] = (r + 0.5) / CAL_ROWS;
-    for (int d = 0; d < nx; ++d) x[1 + d] = nrm();
-    cal_affine(W0, b0, H, n_in, x.data(), a[0].data());
-    for (int k = 0; k < H; ++k) a[0][k] = cal_act(act, a[0][k]);
-    for (int l = 1; l < L; ++l) {
-      cal_affine(W[l], b[l], H, H, a[l - 1].data(), a[l].data());
-      for (int k = 0; k < H; ++k) a[l][k] = cal_act(act, a[l][k]);
-    }
-    for (int l = 0; l + 1 < L; ++l)
-      for (int k = 0; k < H; ++k) sa[l] += a[l][k] * a[l][k];
-    if (r >= 4) continue;  // the tangents (H^2 nx per layer) from the first 4 rows
-    // tangents of every direction at once: z[h][d]
-    for (int h = 0; h < H; ++h)
-      for (int d = 0; d < nx; ++d) z[(size_t)h * nx + d] = W0[(size_t)h * n_in + 1 + d];
-    for (int l = 0; l + 1 < L; ++l) {
-      for (int h = 0; h < H; ++h) {
-        const double f = cal_dact(act, a[l][h]);
-        for (int d = 0; d < nx; ++d) {
-          z[(size_t)h * nx + d] *= f;
-          sb[l] += z[(size_t)h * nx + d] * z[(size_t)h * nx + d];
-        }
-      }
-      std::fill(zn.begin(), zn.end(), 0.0);
-      for (int o = 0; o < H; ++o)
-        for (int k = 0; k < H; ++k) {
-          const double w = W[l + 1][(size_t)o * H + k];
-          if (w != 0.0)
-            for (int d = 0; d < nx; ++d) zn[(size_t)o * nx + d] += w * z[(size_t)k * nx + d];
-        }
-      z.swap(zn);
-    }
-  }
-  for (int l = 0; l < 4; ++l) {
-    ea[l] = l + 1 < L ? x3_exponent(sa[l], (double)CAL_ROWS * H) : 0;
-    eb[l] = l + 1 < L ? x3_exponent(sb[l], 4.0 * H * nx) : 0;
-  }
 }
 
 extern "C" {
@@ -537,7 +278,6 @@ static void take_timer(hipEvent_t& t0, hipEvent_t& t1) {
   t.recorded = true;
 }
 
-
 int dpi_last_error(char* buf, size_t len) {
   if (buf && len) {
     std::strncpy(buf, g_err.c_str(), len - 1);
@@ -545,12 +285,6 @@ int dpi_last_error(char* buf, size_t len) {
   }
   return (int)g_err.size();
 }
-
-int dpi_problem_destroy(dpi_problem p);
-int dpi_net_destroy(dpi_net net);
-}
-static void prep_tags_drop(const void* owner);  // dpi_label_prepare's records naming a destroyed handle
-extern "C" {
 
 static dpi_problem_s* new_problem(int kind, int nx, double alpha, double T) {
   auto* p = new dpi_problem_s();
@@ -654,724 +388,6 @@ int dpi_problem_destroy(dpi_problem p) {
   prep_tags_drop(p);
   for (void* d : p->dev) (void)hipFree(d);
   delete p;
-  return 0;
-}
-
-// The net's ring of sticky status words (DPI_STATUS_*), zeroed, in host-visible memory the kernels
-// write with a vector store and the host reads without a HIP call; and whether every parameter is
-// finite.
-static int net_init_status(dpi_net_s* n, const float* params, size_t n_params) {
-  n->finite = true;
-  for (size_t i = 0; i < n_params; ++i)
-    if (!std::isfinite(params[i])) {
-      n->finite = false;
-      break;
-    }
-  const size_t bytes = (size_t)DPI_STATUS_SLOTS * STATUS_STRIDE * sizeof(int);
-  void* h = nullptr;
-  HIPCHK(hipHostMalloc(&h, bytes, hipHostMallocMapped | hipHostMallocCoherent));
-  std::memset(h, 0, bytes);
-  n->status_host = (int*)h;
-  void* d = nullptr;
-  HIPCHK(hipHostGetDevicePointer(&d, h, 0));
-  n->status = (int*)d;
-  n->slot = 0;
-  return 0;
-}
-
-static volatile int* status_word(dpi_net net, int slot) {
-  return (volatile int*)(net->status_host + (size_t)slot * STATUS_STRIDE);
-}
-
-int dpi_net_create_zero(dpi_net* out) {
-  if (!out) return fail(DPI_ERR_ARG, "null out");
-  auto* n = new dpi_net_s();
-  std::memset(&n->d, 0, sizeof(n->d));
-  n->d.kind = 0;  // u = 0 cannot overflow: no status word (creation stays host-only)
-  *out = n;
-  return 0;
-}
-
-int dpi_net_set_precision(dpi_net net, int mode) {
-  if (!net || mode < -1 || mode > DPI_GEMM_AUTO) return fail(DPI_ERR_ARG, "net_set_precision: bad arguments");
-  net->precision = mode;
-  return 0;
-}
-
-int dpi_net_status(dpi_net net, int clear, void* stream, int* status) {
-  if (!net || !status) return fail(DPI_ERR_ARG, "net_status: bad arguments");
-  int v = 0;
-  if (net->status_host) {
-    HIPCHK(hipStreamSynchronize((hipStream_t)stream));
-    v = *status_word(net, net->slot);
-    if (clear && v) *status_word(net, net->slot) = 0;
-  }
-  *status = v;
-  return 0;
-}
-
-int dpi_net_status_slot(dpi_net net, int slot, int clear) {
-  if (!net || slot < 0 || slot >= DPI_STATUS_SLOTS) return fail(DPI_ERR_ARG, "net_status_slot: bad arguments");
-  net->slot = slot;
-  if (clear && net->status_host) *status_word(net, slot) = 0;
-  return 0;
-}
-
-int dpi_net_status_peek(dpi_net net, int slot, int* status) {
-  if (!net || !status || slot < 0 || slot >= DPI_STATUS_SLOTS)
-    return fail(DPI_ERR_ARG, "net_status_peek: bad arguments");
-  *status = net->status_host ? *status_word(net, slot) : 0;
-  return 0;
-}
-
-// gen_only: the general image alone, whatever the shape (a terminal-enforcing value net has no
-// specialised instance)
-static int mlp_create(int n_in, int n_hidden, const int* widths, int act, const float* params, size_t n_params,
-                      dpi_net* out, bool gen_only) {
-  if (n_in - 1 > NXW_MAX)
-    return fail(DPI_ERR_UNSUPPORTED, "mlp: nx = n_in - 1 exceeds the compiled maximum state dimension 256 (NXW_MAX)");
-  if (!out || !widths || !params || n_in < 2 || n_hidden < 1) return fail(DPI_ERR_ARG, "mlp: bad arguments");
-  if (n_hidden > GEN_LMAX) return fail(DPI_ERR_UNSUPPORTED, "mlp: at most 8 hidden layers (GEN_LMAX)");
-  if (act != DPI_ACT_ELU && act != DPI_ACT_TANH)
-    return fail(DPI_ERR_UNSUPPORTED, "mlp: activations must be DPI_ACT_ELU or DPI_ACT_TANH");
-  // Any hidden widths up to 256, up to 8 layers.  Up to 4 layers of widths <= 128 the net gets the
-  // specialised image: the layers zero-padded to the smallest compiled width H in {16, 32, 64, 128}
-  // that holds the widest one.  A padded unit has zero weights and bias in and zero weights out, so
-  // its activation (ELU(0) = tanh(0) = 0) and every gradient through it add exact zeros: the labels
-  // are those of the unpadded network.  A net without a specialised first-order Cha / OU instance of
-  // its (H, L) also (or only) gets the general family's image, padded the same way to 128 or 256.
-  int wmax = 0;
-  size_t expect = 0;
-  for (int l = 0; l < n_hidden; ++l) {
-    if (widths[l] < 1 || widths[l] > GEN_HMAX)
-      return fail(DPI_ERR_UNSUPPORTED, "mlp: hidden widths must be in [1, 256] (GEN_HMAX)");
-    wmax = std::max(wmax, widths[l]);
-    expect += (size_t)widths[l] * ((l ? widths[l - 1] : n_in) + 1);
-  }
-  expect += (size_t)widths[n_hidden - 1] + 1;
-  if (n_params != expect) return fail(DPI_ERR_ARG, "mlp: parameter count mismatch");
-  const float* const given = params;  // the finiteness scan (range guard) reads the caller's values
-  const int H = wmax <= 16 ? 16 : wmax <= 32 ? 32 : wmax <= 64 ? 64 : wmax <= 128 ? 128 : 256;
-  const int nx = n_in - 1, L = n_hidden;
-  const bool spec = !gen_only && L <= 4 && wmax <= HMAX;    // the specialised image (NetDev)
-  const bool gen = !spec || !spec_shape(DPI_EQ_CHA, H, L);  // the general image (NetGen); Cha and OU share a list
-  // nx padded to 16 (the fp32 weight images) and to 32 (the split ones).  The split layer-1 rows are
-  // LDS chunks of at most 128 words whose 16-B granules are XOR-swizzled by row (split_swz): a closed
-  // permutation only for 8, 16 or 32 granules per row, so a chunk of 96 words (nx in 65..96, or
-  // 193..224 in the wide instances) is padded to 128 with zero columns — and nxp with it, so the path
-  // kernels zero those rows of their noise tile (and the fp32 images carry the same zero columns)
-  int nxp = (nx + 15) & ~15, nxp32 = (nx + 31) & ~31;
-  if ((nxp32 & 127) == 96) nxp = nxp32 = nxp32 + 32;
-  std::vector<float> padded;
-  bool same = true;
-  for (int l = 0; l < n_hidden; ++l) same = same && widths[l] == H;
-  if (!same) {  // re-lay the parameters out as the equal-width-H network
-    padded.assign((size_t)H * n_in + H + (size_t)(L - 1) * (H * H + H) + H + 1, 0.f);
-    const float* src = params;
-    float* dst = padded.data();
-    int win = n_in, wpad_in = n_in;
-    for (int l = 0; l < L; ++l) {
-      const int w = widths[l];
-      for (int r = 0; r < w; ++r)
-        for (int c = 0; c < win; ++c) dst[(size_t)r * wpad_in + c] = src[(size_t)r * win + c];
-      src += (size_t)w * win;
-      dst += (size_t)H * wpad_in;
-      for (int r = 0; r < w; ++r) dst[r] = src[r];
-      src += w;
-      dst += H;
-      win = w;
-      wpad_in = H;
-    }
-    for (int c = 0; c < win; ++c) dst[c] = src[c];
-    dst[H] = src[win];
-    params = padded.data();
-  }
-  // host-side repack
-  std::vector<float> blob;
-  auto take = [&](size_t cnt) {
-    size_t off = blob.size();
-    blob.resize(off + ((cnt + 3) & ~size_t(3)), 0.f);
-    return off;
-  };
-  // ---- the general image: the equal-width-H parameters (above) re-laid with row stride HC
-  const int HC = H <= 128 ? 128 : 256, nxg = (nx + 15) & ~15, nxg32 = (nx + 31) & ~31;
-  size_t gW1x = 0, gw1t = 0, gb1 = 0, gc1 = 0, gW1xT = 0, gW[GEN_LMAX] = {0}, gWT[GEN_LMAX] = {0}, gb[GEN_LMAX] = {0},
-         gwout = 0;
-  float gbout = 0.f;
-  if (gen) {
-    const float* q = params;  // (H, n_in) | (H) | [(H, H) | (H)] x (L - 1) | (H) | 1
-    gW1x = take((size_t)HC * nxg), gw1t = take(HC), gb1 = take(HC), gc1 = take(HC), gW1xT = take((size_t)nxg32 * HC);
-    for (int h = 0; h < H; ++h) {
-      double cs = 0;
-      for (int d = 0; d < nx; ++d) {
-        const float w = q[(size_t)h * n_in + 1 + d];
-        blob[gW1x + (size_t)h * nxg + d] = w;
-        blob[gW1xT + (size_t)d * HC + h] = w;
-        cs += w;
-      }
-      blob[gw1t + h] = q[(size_t)h * n_in];
-      blob[gb1 + h] = q[(size_t)H * n_in + h];
-      blob[gc1 + h] = (float)cs;
-    }
-    q += (size_t)H * n_in + H;
-    for (int l = 1; l < L; ++l) {
-      gW[l] = take((size_t)HC * HC), gWT[l] = take((size_t)HC * HC), gb[l] = take(HC);
-      for (int r = 0; r < H; ++r)
-        for (int c = 0; c < H; ++c) {
-          blob[gW[l] + (size_t)r * HC + c] = q[(size_t)r * H + c];
-          blob[gWT[l] + (size_t)c * HC + r] = q[(size_t)r * H + c];
-        }
-      q += (size_t)H * H;
-      for (int h = 0; h < H; ++h) blob[gb[l] + h] = q[h];
-      q += H;
-    }
-    gwout = take(HC);
-    for (int h = 0; h < H; ++h) blob[gwout + h] = q[h];
-    gbout = q[H];
-  }
-  const float* W0 = params;
-  const float* b0 = W0 + (size_t)H * n_in;
-  size_t oW1x = 0, ow1t = 0, ob1 = 0, oc1 = 0, oW1xT = 0, oW[4] = {0}, oWT[4] = {0}, ob[4] = {0}, owout = 0;
-  float bout = 0.f;
-  size_t oW1xS = 0, oW1xTS = 0, oWS[4] = {0}, oWTS[4] = {0}, oWU[4] = {0};
-  float wus[4] = {1.f, 1.f, 1.f, 1.f};
-  int ea[4] = {0, 0, 0, 0}, eb[4] = {0, 0, 0, 0};  // mlp_hdiag_split's operand exponents
-  if (spec) {
-    oW1x = take((size_t)H * nxp), ow1t = take(H), ob1 = take(H), oc1 = take(H), oW1xT = take((size_t)nxp * H);
-    for (int h = 0; h < H; ++h) {
-      double cs = 0;
-      for (int d = 0; d < nx; ++d) {
-        const float w = W0[(size_t)h * n_in + 1 + d];
-        blob[oW1x + (size_t)h * nxp + d] = w;
-        blob[oW1xT + (size_t)d * H + h] = w;
-        cs += w;
-      }
-      blob[ow1t + h] = W0[(size_t)h * n_in];
-      blob[ob1 + h] = b0[h];
-      blob[oc1 + h] = (float)cs;
-    }
-    const float* cur = b0 + H;
-    for (int l = 1; l < L; ++l) {
-      oW[l] = take((size_t)H * H);
-      oWT[l] = take((size_t)H * H);
-      ob[l] = take(H);
-      for (int r = 0; r < H; ++r)
-        for (int c = 0; c < H; ++c) {
-          blob[oW[l] + (size_t)r * H + c] = cur[(size_t)r * H + c];
-          blob[oWT[l] + (size_t)c * H + r] = cur[(size_t)r * H + c];
-        }
-      cur += (size_t)H * H;
-      for (int h = 0; h < H; ++h) blob[ob[l] + h] = cur[h];
-      cur += H;
-    }
-    owout = take(H);
-    for (int h = 0; h < H; ++h) blob[owout + h] = cur[h];
-    bout = cur[H];
-    // fp16-split copies for the split MFMA path (H % 32 == 0)
-    if (H % 32 == 0) {
-      auto Wx = [&](int h, int d) { return d < nx ? W0[(size_t)h * n_in + 1 + d] : 0.f; };
-      oW1xS = pack_split(blob, H, nxp32, Wx);
-      oW1xTS = pack_split(blob, nxp32, H, [&](int d, int h) { return Wx(h, d); });
-      for (int l = 1; l < L; ++l) {
-        const float* Wl = blob.data() + oW[l];
-        std::vector<float> Wc(Wl, Wl + (size_t)H * H);
-        oWS[l] = pack_split(blob, H, H, [&](int r, int c) { return Wc[(size_t)r * H + c]; });
-        oWTS[l] = pack_split(blob, H, H, [&](int r, int c) { return Wc[(size_t)c * H + r]; });
-        oWU[l] = pack_split_x3(blob, H, H, [&](int r, int c) { return Wc[(size_t)r * H + c]; }, &wus[l]);
-      }
-      const float *Wl[4] = {nullptr, nullptr, nullptr, nullptr}, *bl[4] = {nullptr, nullptr, nullptr, nullptr};
-      for (int l = 1; l < L; ++l) Wl[l] = blob.data() + oW[l], bl[l] = blob.data() + ob[l];
-      mlp_calibrate(nx, H, L, act, W0, b0, Wl, bl, ea, eb);
-    }
-  }
-  auto* n = new dpi_net_s();
-  std::memset(&n->d, 0, sizeof(n->d));
-  void* d = nullptr;
-  if (hipMalloc(&d, blob.size() * sizeof(float)) != hipSuccess) {
-    delete n;
-    return fail(DPI_ERR_HIP, "mlp: hipMalloc failed");
-  }
-  if (hipMemcpy(d, blob.data(), blob.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
-    (void)hipFree(d);
-    delete n;
-    return fail(DPI_ERR_HIP, "mlp: hipMemcpy failed");
-  }
-  const float* base = reinterpret_cast<const float*>(d);
-  n->blob = d;
-  n->n_in = n_in;
-  n->d.kind = 1;
-  n->d.H = H;
-  n->d.L = L;
-  n->d.nxp = nxp;
-  n->d.act = act;
-  n->spec = spec;
-  n->gen = gen;
-  if (gen) {
-    NetGen& g = n->g;
-    g.H = HC, g.L = L, g.nxp = nxg, g.act = act, g.ht = ((wmax + 31) & ~31) / 16;
-    g.W1x = base + gW1x, g.w1t = base + gw1t, g.b1 = base + gb1, g.c1 = base + gc1, g.W1xT = base + gW1xT;
-    for (int l = 1; l < L; ++l) g.W[l] = base + gW[l], g.WT[l] = base + gWT[l], g.b[l] = base + gb[l];
-    g.wout = base + gwout, g.bout = gbout;
-  }
-  if (spec) {
-    n->d.W1x = base + oW1x;
-    n->d.w1t = base + ow1t;
-    n->d.b1 = base + ob1;
-    n->d.c1 = base + oc1;
-    n->d.W1xT = base + oW1xT;
-    for (int l = 1; l < L; ++l) {
-      n->d.W[l] = base + oW[l];
-      n->d.WT[l] = base + oWT[l];
-      n->d.b[l] = base + ob[l];
-    }
-    n->d.wout = base + owout;
-    n->d.bout = bout;
-    n->d.nxp32 = nxp32;
-  }
-  if (spec && H % 32 == 0) {
-    auto u32 = [&](size_t off) { return reinterpret_cast<const uint32_t*>(base + off); };
-    n->d.W1xS = u32(oW1xS);
-    n->d.W1xTS = u32(oW1xTS);
-    for (int l = 1; l < L; ++l) {
-      n->d.WS[l] = u32(oWS[l]);
-      n->d.WTS[l] = u32(oWTS[l]);
-      n->d.WU[l] = u32(oWU[l]);
-      n->d.wus[l] = wus[l];
-    }
-    // mlp_hdiag_split: forward operand of layer l + 1 = 2^ea[l] a_l, tangent operand = 2^eb[l] act'(a_l) z_l
-    for (int l = 0; l < L; ++l) {
-      n->d.hsa[l] = std::ldexp(1.0f, ea[l]);
-      if (l >= 1) n->d.hsc[l] = std::ldexp(wus[l], -ea[l - 1]);
-      n->d.hzs[l] = l == 0 ? 1.0f : std::ldexp(wus[l], -eb[l - 1]);
-      n->d.hbs[l] = l == 0 ? std::ldexp(1.0f, eb[0]) : std::ldexp(wus[l], eb[l] - eb[l - 1]);
-    }
-  }
-  if (int rc = net_init_status(n, given, n_params)) {
-    dpi_net_destroy(n);
-    return rc;
-  }
-  *out = n;
-  return 0;
-}
-
-int dpi_net_create_mlp(int n_in, int n_hidden, const int* widths, int act, const float* params, size_t n_params,
-                       dpi_net* out) {
-  return mlp_create(n_in, n_hidden, widths, act, params, n_params, out, false);
-}
-
-// A terminal-enforcing net (include/dpi.h): the value net's or the OnlyGradient head's general image,
-// marked so that the pair routes to the TERMA kernels (dpi_general.h).
-int dpi_net_create_mlp_terminal(int n_in, int n_hidden, const int* widths, int act, int head, double T,
-                                const float* params, size_t n_params, dpi_net* out) {
-  if (head == DPI_HEAD_VALUE_GRADIENT)
-    return fail(DPI_ERR_ARG, "mlp_terminal: a terminal-enforcing net is DPI_HEAD_VALUE or DPI_HEAD_GRADIENT; the "
-                             "reference raises ValueError for ValueGradient (picard/solution_enforce_terminal.py:18-19)");
-  if (head != DPI_HEAD_VALUE && head != DPI_HEAD_GRADIENT)
-    return fail(DPI_ERR_ARG, "mlp_terminal: head must be DPI_HEAD_VALUE or DPI_HEAD_GRADIENT");
-  if (!(T > 0.0) || !std::isfinite(T)) return fail(DPI_ERR_ARG, "mlp_terminal: T must be positive and finite");
-  if (!out) return fail(DPI_ERR_ARG, "mlp: bad arguments");
-  dpi_net n = nullptr;
-  const int rc = head == DPI_HEAD_VALUE ? mlp_create(n_in, n_hidden, widths, act, params, n_params, &n, true)
-                                        : dpi_net_create_mlp_head(n_in, n_hidden, widths, act, head, params, n_params, &n);
-  if (rc) return rc;
-  n->term = true;
-  n->term_T = (float)T;
-  *out = n;
-  return 0;
-}
-
-// A gradient-head net (include/dpi.h): the general image only (dpi_general.h NetGenHead), whatever the
-// widths — built straight from the caller's rows with row stride HC, zero-padded as above.
-int dpi_net_create_mlp_head(int n_in, int n_hidden, const int* widths, int act, int head, const float* params,
-                            size_t n_params, dpi_net* out) {
-  if (head == DPI_HEAD_VALUE) return dpi_net_create_mlp(n_in, n_hidden, widths, act, params, n_params, out);
-  if (n_in - 1 > NXW_MAX)
-    return fail(DPI_ERR_UNSUPPORTED, "mlp: nx = n_in - 1 exceeds the compiled maximum state dimension 256 (NXW_MAX)");
-  if (!out || !widths || !params || n_in < 2 || n_hidden < 1) return fail(DPI_ERR_ARG, "mlp: bad arguments");
-  if (n_hidden > GEN_LMAX) return fail(DPI_ERR_UNSUPPORTED, "mlp: at most 8 hidden layers (GEN_LMAX)");
-  if (act != DPI_ACT_ELU && act != DPI_ACT_TANH)
-    return fail(DPI_ERR_UNSUPPORTED, "mlp: activations must be DPI_ACT_ELU or DPI_ACT_TANH");
-  if (head != DPI_HEAD_VALUE_GRADIENT && head != DPI_HEAD_GRADIENT)
-    return fail(DPI_ERR_ARG, "mlp_head: head must be DPI_HEAD_VALUE, DPI_HEAD_VALUE_GRADIENT or DPI_HEAD_GRADIENT");
-  const int nx = n_in - 1, L = n_hidden;
-  const bool value = head == DPI_HEAD_VALUE_GRADIENT;
-  const int n_out = value ? 1 + nx : nx;
-  int wmax = 0;
-  size_t expect = 0;
-  for (int l = 0; l < L; ++l) {
-    if (widths[l] < 1 || widths[l] > GEN_HMAX)
-      return fail(DPI_ERR_UNSUPPORTED, "mlp: hidden widths must be in [1, 256] (GEN_HMAX)");
-    wmax = std::max(wmax, widths[l]);
-    expect += (size_t)widths[l] * ((l ? widths[l - 1] : n_in) + 1);
-  }
-  const int wl = widths[L - 1];
-  expect += (size_t)n_out * (wl + 1);
-  if (n_params != expect)
-    return fail(DPI_ERR_ARG, value ? "mlp_head: parameter count mismatch (a ValueGradient head has 1 + nx output rows)"
-                                   : "mlp_head: parameter count mismatch (an OnlyGradient head has nx output rows)");
-  const int HC = wmax <= 128 ? 128 : 256, nxg = (nx + 15) & ~15, nxg32 = (nx + 31) & ~31;
-  std::vector<float> blob;
-  auto take = [&](size_t cnt) {
-    size_t off = blob.size();
-    blob.resize(off + ((cnt + 3) & ~size_t(3)), 0.f);
-    return off;
-  };
-  const size_t gW1x = take((size_t)HC * nxg), gw1t = take(HC), gb1 = take(HC), gW1xT = take((size_t)nxg32 * HC);
-  size_t gW[GEN_LMAX] = {0}, gWT[GEN_LMAX] = {0}, gb[GEN_LMAX] = {0};
-  const float* q = params;
-  for (int h = 0; h < widths[0]; ++h) {
-    for (int d = 0; d < nx; ++d) {
-      const float w = q[(size_t)h * n_in + 1 + d];
-      blob[gW1x + (size_t)h * nxg + d] = w;
-      blob[gW1xT + (size_t)d * HC + h] = w;
-    }
-    blob[gw1t + h] = q[(size_t)h * n_in];
-    blob[gb1 + h] = q[(size_t)widths[0] * n_in + h];
-  }
-  q += (size_t)widths[0] * (n_in + 1);
-  for (int l = 1; l < L; ++l) {
-    const int w = widths[l], win = widths[l - 1];
-    gW[l] = take((size_t)HC * HC), gWT[l] = take((size_t)HC * HC), gb[l] = take(HC);
-    for (int r = 0; r < w; ++r)
-      for (int c = 0; c < win; ++c) {
-        blob[gW[l] + (size_t)r * HC + c] = q[(size_t)r * win + c];
-        blob[gWT[l] + (size_t)c * HC + r] = q[(size_t)r * win + c];
-      }
-    q += (size_t)w * win;
-    for (int h = 0; h < w; ++h) blob[gb[l] + h] = q[h];
-    q += w;
-  }
-  // the last Linear: [value row |] nx gradient rows, then their biases; cg and sum bg in fp64
-  const size_t gwout = take(HC), gcg = take(HC), gG = take((size_t)nxg32 * HC), gbg = take(nxg32);
-  const float* const Wg = q + (value ? wl : 0);
-  const float* const bo = q + (size_t)n_out * wl;
-  for (int h = 0; h < wl; ++h) {
-    double cs = 0;
-    for (int d = 0; d < nx; ++d) {
-      const float w = Wg[(size_t)d * wl + h];
-      blob[gG + (size_t)d * HC + h] = w;
-      cs += w;
-    }
-    blob[gcg + h] = (float)cs;
-    if (value) blob[gwout + h] = q[h];
-  }
-  double bs = 0;
-  for (int d = 0; d < nx; ++d) {
-    blob[gbg + d] = bo[(value ? 1 : 0) + d];
-    bs += bo[(value ? 1 : 0) + d];
-  }
-  auto* n = new dpi_net_s();
-  std::memset(&n->d, 0, sizeof(n->d));
-  void* d = nullptr;
-  if (hipMalloc(&d, blob.size() * sizeof(float)) != hipSuccess) {
-    delete n;
-    return fail(DPI_ERR_HIP, "mlp_head: hipMalloc failed");
-  }
-  if (hipMemcpy(d, blob.data(), blob.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
-    (void)hipFree(d);
-    delete n;
-    return fail(DPI_ERR_HIP, "mlp_head: hipMemcpy failed");
-  }
-  const float* base = reinterpret_cast<const float*>(d);
-  n->blob = d;
-  n->n_in = n_in;
-  n->d.kind = 1;
-  n->d.H = HC;
-  n->d.L = L;
-  n->d.nxp = nxg;
-  n->d.act = act;
-  n->spec = false;
-  n->gen = true;
-  n->head = head;
-  NetGenHead& g = n->hd;
-  g.H = HC, g.L = L, g.nxp = nxg, g.act = act, g.ht = ((wmax + 31) & ~31) / 16;
-  g.W1x = base + gW1x, g.w1t = base + gw1t, g.b1 = base + gb1, g.c1 = base + gcg, g.W1xT = base + gW1xT;
-  for (int l = 1; l < L; ++l) g.W[l] = base + gW[l], g.WT[l] = base + gWT[l], g.b[l] = base + gb[l];
-  g.wout = base + gwout, g.bout = value ? bo[0] : 0.f;
-  g.value = value ? 1 : 0, g.G = base + gG, g.bg = base + gbg, g.bgsum = (float)bs;
-  n->g = g;  // the NetGen part: what the workspace layout and the routing read
-  if (int rc = net_init_status(n, params, n_params)) {
-    dpi_net_destroy(n);
-    return rc;
-  }
-  *out = n;
-  return 0;
-}
-
-int dpi_net_create_pisgrad(int nx, int n_hidden, const int* hidden, double T, const float* params, size_t n_params,
-                           dpi_net* out) {
-  if (nx > NXP_MAX)
-    return fail(DPI_ERR_UNSUPPORTED, "pisgrad: nx exceeds the compiled maximum state dimension 128 (NXP_MAX)");
-  if (!out || !hidden || !params || nx < 1 || n_hidden < 1 || n_hidden > 4)
-    return fail(DPI_ERR_ARG, "pisgrad: bad arguments (1 <= n_hidden <= 4, nx <= 128)");
-  for (int l = 0; l < n_hidden; ++l)
-    if (hidden[l] < 4 || hidden[l] > 1024 || (hidden[l] % 4)) return fail(DPI_ERR_ARG, "pisgrad: hidden widths % 4");
-  const int C = PIS_CH, nsm = n_hidden, L = n_hidden, IN = C + nx;
-  // expected parameter count in state-dict order (solution.py:160-205)
-  size_t expect = 2 * C + (size_t)C * 2 * C + C + (size_t)C * C + C;   // phase, coeff, t_encoder
-  expect += (size_t)C * 2 * C + C + (size_t)nsm * (C * C + C) + (size_t)nx * C + nx;  // smooth_net
-  int in = IN;
-  for (int l = 0; l < L; ++l) {
-    expect += (size_t)hidden[l] * in + hidden[l];
-    in = hidden[l];
-  }
-  expect += (size_t)nx * in + nx;
-  if (n_params != expect) return fail(DPI_ERR_ARG, "pisgrad: parameter count mismatch");
-  const float* q = params;
-  auto take_src = [&](size_t cnt) {
-    const float* r = q;
-    q += cnt;
-    return r;
-  };
-  std::vector<float> blob;
-  auto put = [&](const float* src, size_t cnt) {
-    size_t off = blob.size();
-    blob.resize(off + ((cnt + 3) & ~size_t(3)), 0.f);
-    std::memcpy(blob.data() + off, src, cnt * sizeof(float));
-    return off;
-  };
-  auto putT = [&](const float* src, int rows, int cols, int c0, int nc) {  // (src[:, c0:c0+nc])^T
-    size_t off = blob.size();
-    blob.resize(off + (((size_t)nc * rows + 3) & ~size_t(3)), 0.f);
-    for (int r = 0; r < rows; ++r)
-      for (int c = 0; c < nc; ++c) blob[off + (size_t)c * rows + r] = src[(size_t)r * cols + c0 + c];
-    return off;
-  };
-  const float* phase = take_src(C);
-  const float* coeff = take_src(C);
-  const float* te0 = take_src((size_t)C * 2 * C);
-  const float* te0b = take_src(C);
-  const float* te2 = take_src((size_t)C * C);
-  const float* te2b = take_src(C);
-  const float* sn0 = take_src((size_t)C * 2 * C);
-  const float* sn0b = take_src(C);
-  const float *snw[4], *snbw[4];
-  for (int j = 0; j < nsm; ++j) {
-    snw[j] = take_src((size_t)C * C);
-    snbw[j] = take_src(C);
-  }
-  const float* snl = take_src((size_t)nx * C);
-  const float* snlb = take_src(nx);
-  const float *nnw[5], *nnbw[5];
-  int ins[5];
-  in = IN;
-  for (int l = 0; l <= L; ++l) {
-    const int o = l < L ? hidden[l] : nx;
-    nnw[l] = take_src((size_t)o * in);
-    nnbw[l] = take_src(o);
-    ins[l] = in;
-    in = o;
-  }
-  // smooth0 = smooth_net(emb(0))[0] in double on the host
-  double smooth0;
-  {
-    std::vector<double> e(2 * C), h(C), h2(C);
-    for (int j = 0; j < C; ++j) {
-      e[j] = std::sin((double)phase[j]);
-      e[C + j] = std::cos((double)phase[j]);
-    }
-    auto elu_d = [](double z) { return z > 0 ? z : std::expm1(z); };
-    for (int o = 0; o < C; ++o) {
-      double a = sn0b[o];
-      for (int k = 0; k < 2 * C; ++k) a += (double)sn0[(size_t)o * 2 * C + k] * e[k];
-      h[o] = a;
-    }
-    for (int j = 0; j < nsm; ++j) {
-      for (int o = 0; o < C; ++o) {
-        double a = snbw[j][o];
-        for (int k = 0; k < C; ++k) a += (double)snw[j][(size_t)o * C + k] * elu_d(h[k]);
-        h2[o] = a;
-      }
-      h.swap(h2);
-    }
-    double a = snlb[0];
-    for (int k = 0; k < C; ++k) a += (double)snl[k] * elu_d(h[k]);
-    smooth0 = a;
-  }
-  const PisExps ex =
-      pis_calibrate(nx, L, hidden, T, phase, coeff, te0, te0b, te2, te2b, sn0, sn0b, snw, snbw, nsm, nnw, nnbw, ins);
-  NetPisDev pd;
-  std::memset(&pd, 0, sizeof(pd));
-  size_t o_phase = put(phase, C), o_coeff = put(coeff, C), o_te0 = put(te0, (size_t)C * 2 * C), o_te0b = put(te0b, C),
-         o_te2 = put(te2, (size_t)C * C), o_te2b = put(te2b, C), o_sn0 = put(sn0, (size_t)C * 2 * C),
-         o_sn0b = put(sn0b, C), o_snl = put(snl, C), o_snlb = put(snlb, 1);
-  size_t o_sn[4], o_snb[4], o_nn[5], o_nnb[5], o_nnT[5];
-  for (int j = 0; j < nsm; ++j) {
-    o_sn[j] = put(snw[j], (size_t)C * C);
-    o_snb[j] = put(snbw[j], C);
-  }
-  for (int l = 0; l <= L; ++l) {
-    const int o = l < L ? hidden[l] : nx;
-    o_nn[l] = put(nnw[l], (size_t)o * ins[l]);
-    o_nnb[l] = put(nnbw[l], o);
-    o_nnT[l] = l == 0 ? putT(nnw[0], hidden[0], ins[0], C, nx) : putT(nnw[l], o, ins[l], 0, ins[l]);
-  }
-  // split-storage copies (k_gemm_x3): output dims padded to 64 (hp_l, NOP), input dims to 32
-  // (INP = IN's width, NXK = the x part of IN), zero fill, 128-B aligned rows
-  auto r64 = [](int x) { return (x + 63) & ~63; };
-  const int INP = (C + nx + 31) & ~31, NXK = (nx + 31) & ~31, NOP = r64(nx);
-  int hp[4];
-  for (int l = 0; l < L; ++l) hp[l] = r64(hidden[l]);
-  size_t s_te0, s_te2, s_sn0, s_sn[4] = {0}, s_nn[5] = {0}, s_nnT[5] = {0}, s_nnbP[5] = {0}, s_gxno = 0;
-  size_t s_nnF[5] = {0}, s_nnTF[5] = {0}, s_gxnoF = 0;
-  float w_te0 = 1.f, w_te2 = 1.f, w_sn0 = 1.f, w_sn[4] = {1.f, 1.f, 1.f, 1.f}, w_nn[5], w_nnT[5], w_gxno = 1.f;
-  {
-    auto align = [&]() { blob.resize((blob.size() + 31) & ~size_t(31), 0.f); };
-    auto packm = [&](const float* src, int rows, int cols, int Np, int Kp, bool trans, float* ws) {
-      align();
-      return pack_split_x3(blob, Np, Kp, [&](int r, int c) {
-        if (trans) return (c < rows && r < cols) ? src[(size_t)c * cols + r] : 0.f;  // (src^T)[r][c]
-        return (r < rows && c < cols) ? src[(size_t)r * cols + c] : 0.f;
-      }, ws);
-    };
-    // every product's weight scale carries its stored input's 2^-e (x3_exponent); the VJP's also
-    // its output's 2^e (EPI_DELU stores (acc ws) elu'(A))
-    s_te0 = packm(te0, C, 2 * C, C, 2 * C, false, &w_te0);
-    s_te2 = packm(te2, C, C, C, C, false, &w_te2);
-    w_te2 = std::ldexp(w_te2, -ex.te);
-    s_sn0 = packm(sn0, C, 2 * C, C, 2 * C, false, &w_sn0);
-    for (int j = 0; j < nsm; ++j) {
-      s_sn[j] = packm(snw[j], C, C, C, C, false, &w_sn[j]);
-      w_sn[j] = std::ldexp(w_sn[j], -ex.sn[j]);
-    }
-    // forward: nn[0] (h0 x (64 + nx)), nn[l] (h_l x h_{l-1}), nn[L] (nx x h_{L-1}); nn[0]'s t_emb
-    // columns carry t_emb's 2^-e (IN holds [2^e t_emb | X], two operands in one K)
-    {
-      align();
-      const float* w0 = nnw[0];
-      const int in0 = ins[0], h0 = hidden[0];
-      s_nn[0] = pack_split_x3(blob, hp[0], INP, [&](int r, int c) {
-        if (r >= h0 || c >= in0) return 0.f;
-        return c < C ? std::ldexp(w0[(size_t)r * in0 + c], -ex.temb) : w0[(size_t)r * in0 + c];
-      }, &w_nn[0]);
-    }
-    for (int l = 1; l < L; ++l) {
-      s_nn[l] = packm(nnw[l], hidden[l], ins[l], hp[l], hp[l - 1], false, &w_nn[l]);
-      w_nn[l] = std::ldexp(w_nn[l], -ex.a[l - 1]);
-    }
-    s_nn[L] = packm(nnw[L], nx, ins[L], NOP, hp[L - 1], false, &w_nn[L]);
-    w_nn[L] = std::ldexp(w_nn[L], -ex.a[L - 1]);
-    // VJP: nnT[L] = nn[L]^T (h_{L-1} x nx), nnT[l] = nn[l]^T, nnT[0] = nn[0][:, 64:]^T (nx x h0)
-    s_nnT[L] = packm(nnw[L], nx, ins[L], hp[L - 1], NXK, true, &w_nnT[L]);
-    w_nnT[L] = std::ldexp(w_nnT[L], ex.d[L - 1]);
-    for (int l = 1; l < L; ++l) {
-      s_nnT[l] = packm(nnw[l], hidden[l], ins[l], hp[l - 1], hp[l], true, &w_nnT[l]);
-      w_nnT[l] = std::ldexp(w_nnT[l], ex.d[l - 1] - ex.d[l]);
-    }
-    {
-      align();
-      const float* w0 = nnw[0];
-      const int in0 = ins[0], h0 = hidden[0];
-      s_nnT[0] = pack_split_x3(blob, NOP, hp[0], [&](int d, int h) {
-        return (d < nx && h < h0) ? w0[(size_t)h * in0 + C + d] : 0.f;
-      }, &w_nnT[0]);
-    }
-    {  // [nnT[0] | nn[L]]: row d, columns h < hp0 from nn[0][h][64 + d], then nn[L][d][k]
-      align();
-      const float *w0 = nnw[0], *wl = nnw[L];
-      const int in0 = ins[0], h0 = hidden[0], inl = ins[L];
-      // K order [A_{L-1} | D_0]: k_pis_net forms the A_{L-1} half while A_{L-1} is still in LDS
-      // (the two halves' columns carry 2^-e of A_{L-1} resp. D_0)
-      s_gxno = pack_split_x3(blob, NOP, hp[L - 1] + hp[0], [&](int d, int k) {
-        if (d >= nx) return 0.f;
-        if (k < hp[L - 1]) return k < inl ? std::ldexp(wl[(size_t)d * inl + k], -ex.a[L - 1]) : 0.f;
-        k -= hp[L - 1];
-        return k < h0 ? std::ldexp(w0[(size_t)k * in0 + C + d], -ex.d[0]) : 0.f;
-      }, &w_gxno);
-    }
-    for (int l = 0; l <= L; ++l) {
-      s_nnF[l] = pack_frag_major(blob, s_nn[l], l < L ? hp[l] : NOP, l == 0 ? INP : hp[l - 1]);
-      s_nnTF[l] = pack_frag_major(blob, s_nnT[l], l == 0 ? NOP : hp[l - 1], l == 0 ? hp[0] : l == L ? NXK : hp[l]);
-    }
-    s_gxnoF = pack_frag_major(blob, s_gxno, NOP, hp[L - 1] + hp[0]);
-    for (int l = 0; l <= L; ++l) {
-      const int o = l < L ? hidden[l] : nx, op = l < L ? hp[l] : NOP;
-      align();
-      s_nnbP[l] = blob.size();
-      blob.resize(blob.size() + op, 0.f);
-      for (int k = 0; k < o; ++k) blob[s_nnbP[l] + k] = nnbw[l][k];
-    }
-  }
-  auto* n = new dpi_net_s();
-  std::memset(&n->d, 0, sizeof(n->d));
-  void* d = nullptr;
-  if (hipMalloc(&d, blob.size() * sizeof(float)) != hipSuccess ||
-      hipMemcpy(d, blob.data(), blob.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
-    if (d) (void)hipFree(d);
-    delete n;
-    return fail(DPI_ERR_HIP, "pisgrad: device upload failed");
-  }
-  const float* base = reinterpret_cast<const float*>(d);
-  pd.nx = nx;
-  pd.L = L;
-  pd.nsm = nsm;
-  for (int l = 0; l < L; ++l) pd.h[l] = hidden[l];
-  pd.T = (float)T;
-  pd.smooth0 = (float)smooth0;
-  pd.phase = base + o_phase;
-  pd.coeff = base + o_coeff;
-  pd.te0 = base + o_te0;
-  pd.te0b = base + o_te0b;
-  pd.te2 = base + o_te2;
-  pd.te2b = base + o_te2b;
-  pd.sn0 = base + o_sn0;
-  pd.sn0b = base + o_sn0b;
-  for (int j = 0; j < nsm; ++j) {
-    pd.sn[j] = base + o_sn[j];
-    pd.snb[j] = base + o_snb[j];
-  }
-  pd.snlast = base + o_snl;
-  pd.snlastb = base + o_snlb;
-  for (int l = 0; l <= L; ++l) {
-    pd.nn[l] = base + o_nn[l];
-    pd.nnb[l] = base + o_nnb[l];
-    pd.nnT[l] = base + o_nnT[l];
-  }
-  {
-    auto u32 = [&](size_t off) { return reinterpret_cast<const uint32_t*>(base + off); };
-    pd.te0S = u32(s_te0);
-    pd.te2S = u32(s_te2);
-    pd.sn0S = u32(s_sn0);
-    pd.te0W = w_te0, pd.te2W = w_te2, pd.sn0W = w_sn0;
-    for (int j = 0; j < nsm; ++j) pd.snS[j] = u32(s_sn[j]), pd.snW[j] = w_sn[j];
-    pd.gxnoS = u32(s_gxno);
-    pd.gxnoF = u32(s_gxnoF);
-    pd.gxnoW = w_gxno;
-    pd.xs_te = std::ldexp(1.0f, ex.te);
-    pd.xs_temb = std::ldexp(1.0f, ex.temb);
-    for (int j = 0; j < 4; ++j) pd.xs_sn[j] = std::ldexp(1.0f, ex.sn[j]);
-    for (int l = 0; l < 4; ++l) {
-      pd.nnO[l] = std::ldexp(1.0f, ex.a[l]);
-      pd.nnA[l] = std::ldexp(1.0f, -ex.a[l]);
-    }
-    for (int l = 0; l <= L; ++l) {
-      pd.nnS[l] = u32(s_nn[l]);
-      pd.nnTS[l] = u32(s_nnT[l]);
-      pd.nnF[l] = u32(s_nnF[l]);
-      pd.nnTF[l] = u32(s_nnTF[l]);
-      pd.nnW[l] = w_nn[l];
-      pd.nnTW[l] = w_nnT[l];
-      pd.nnbP[l] = base + s_nnbP[l];
-    }
-  }
-  n->blob = d;
-  n->n_in = 1 + nx;
-  n->d.kind = 2;
-  n->pis = pd;
-  if (int rc = net_init_status(n, params, n_params)) {
-    dpi_net_destroy(n);
-    return rc;
-  }
-  *out = n;
-  return 0;
-}
-
-int dpi_net_destroy(dpi_net net) {
-  if (!net) return 0;
-  prep_tags_drop(net);
-  if (net->blob) (void)hipFree(net->blob);
-  if (net->status_host) (void)hipHostFree(net->status_host);
-  delete net;
   return 0;
 }
 
@@ -2402,7 +1418,7 @@ static std::unordered_map<const void*, PrepTag>& prep_tags() {
   return m;
 }
 
-static void prep_tags_drop(const void* owner) {
+void prep_tags_drop(const void* owner) {
   std::lock_guard<std::mutex> g(g_prep_mu);
   for (auto it = prep_tags().begin(); it != prep_tags().end();)
     it = (it->second.p == owner || it->second.net == owner) ? prep_tags().erase(it) : std::next(it);

@@ -60,6 +60,7 @@ SIGNATURES = {
     "dpi_build_id": (c_int, [ctypes.c_char_p, c_size_t]),
     "dpi_launch_timer_arm": (c_int, [c_int]),
     "dpi_launch_timer_ms": (c_int, [c_int, P(ctypes.c_float)]),
+    "dpi_launch_units": (c_int, [P(c_int), P(c_int), P(c_int)]),
     "dpi_workspace_bytes": (c_size_t, [c_void_p, c_void_p, c_int, c_int]),
     "dpi_workspace_bytes_prepared": (c_size_t, [c_void_p, c_void_p, c_int, c_int]),
     "dpi_sample_points": (c_int, [c_void_p, c_int, c_uint64, c_uint32, c_uint32, c_float, c_void_p, c_void_p]),

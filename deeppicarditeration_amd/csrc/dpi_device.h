@@ -36,6 +36,7 @@
 #include "../../include/dpi.h"
 #include "dpi_eq.h"
 #include "dpi_rng.h"
+#include "dpi_tail_units.h"
 
 namespace dpi {
 
@@ -1859,10 +1860,19 @@ struct PathArgs {
   // one row of PARK_ROW floats per path block of the call, indexed by the block id, in which a
   // terminal-first block keeps its terminal sums across the MLP.
   float* park;
+  // Tail units (dpi_tail_units.h; parking instances with a park and both estimators): the last `tail`
+  // path blocks of the call run as a T-unit and an I-unit each, the split part in tail_order (0: I-units
+  // first).  0: whole blocks only.  tail_seq: the launch's join sequence (never 0; a join word holds
+  // ready_word(tail_seq) once one unit of the block has arrived).  unit0: the launch's first grid
+  // index in the map (the two-launch form of the tests; 0 otherwise).
+  int tail, tail_order;
+  uint32_t tail_seq;
+  unsigned unit0;
 };
 // A park row: [wave 4][dim-block NXP_MAX / 16][lane 64][4] floats (32 KB), each wave's 16-B stores
 // and loads contiguous over its lanes.
 constexpr int PARK_ROW = 4 * (NXP_MAX / 16) * 64 * 4;
+static_assert(PARK_ROW == TAIL_PARK_ROW, "dpi_tail_units.h lays the extra rows out in park rows");
 
 // The fused per-point baseline of k_paths_fb (dpi_sample_with_gradients as one launch: first-order
 // Cha / OU labels of MLP and zero nets, no TD), an argument of that kernel only: blocks
@@ -2247,6 +2257,37 @@ __device__ __forceinline__ void fused_reduce(const PathArgs& a, int i, int F, co
   if (threadIdx.x == 0) a.tickets[i] = 0;
 }
 
+// The join of a split block's two units (dpi_tail_units.h): each unit publishes what it hands over as
+// fused_reduce publishes a slab row — every storing wave waits for its stores, a workgroup barrier,
+// one lane's agent-scope release — then exchanges the launch's word into the block's join word.  The
+// unit that finds the word already there is the second: it acquires (agent scope: the first may have
+// run on another XCD) and finishes the block; the first leaves.  Nobody waits.  A word left by an
+// earlier launch, or never written, is not this launch's (ready_word of a sequence that is never 0),
+// so the join words need no zeroing and survive the reuse of the workspace.
+// The second clears the word behind itself, as fused_reduce resets the point's ticket (nobody else
+// touches the word once both units have exchanged).  A launch captured into a graph carries the same
+// sequence in every replay: without the clear, the first unit of a replay would find its own word from
+// the replay before and finish the block from the partner's rows of that replay.
+__device__ __forceinline__ bool tail_join(unsigned long long* word, uint32_t seq) {
+  __shared__ int second;
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's hand-over stores complete
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    const unsigned long long mine = ready_word(seq);
+    const int is_second = __hip_atomic_exchange(word, mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == mine;
+    if (is_second) {
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __hip_atomic_store(word, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    second = is_second;
+  }
+  __syncthreads();
+  return second != 0;
+}
+
 // The path launch: one workgroup per (point, 64-path block).
 // Two workgroups per CU (256 registers per wave) except GBM / TD (one: their LDS) and the exact-fp32
 // OU 4 x 128 instance — the range guard's fallback for OU MLP nets — whose GMM statistics beside
@@ -2255,6 +2296,12 @@ __device__ __forceinline__ void fused_reduce(const PathArgs& a, int i, int F, co
 template <int KIND, int H, int L, bool SPLIT, bool TD, int NXW = NXP_MAX>
 constexpr int k_paths_wgs() {
   return (KIND == DPI_EQ_GBM || TD || NXW > NXP_MAX || (KIND == DPI_EQ_OU && !SPLIT && H == 128 && L == 4)) ? 1 : 2;
+}
+// The fp16-split first-order Cha / OU instances (nx <= 128, no TD) that park (paths_body PARK) and
+// whose launches may end in tail units: all but OU 4 x 128 ELU, which spills with the park.  The host
+// (dpi_kernels.hip tail_count) sizes the grid by the same function.
+constexpr bool tail_shape(int kind, int H, int L, int act) {
+  return kind != DPI_EQ_GBM && H % 32 == 0 && !(kind == DPI_EQ_OU && H == 128 && L == 4 && act == DPI_ACT_ELU);
 }
 // The path launch body; FBT: the one-launch sample_with_gradients form (k_paths_fb), whose first
 // fb.nbase blocks are the points' base blocks — a kernel of its own, so the plain k_paths keeps its
@@ -2291,17 +2338,33 @@ __device__ __forceinline__ void paths_body(const EqDev& e, const NET& net, const
   constexpr bool FBC = FBT && !GBM && !HESS && !TD;
   static_assert(FBC || !FBT, "the fused baseline: first-order Cha / OU labels, no TD");
   constexpr bool FB = FBC;
+  // the instances whose launches may end in tail units: the parking ones (PARK below) that keep their
+  // registers with the units (TAIL_SPILLS: none of them spills)
+  constexpr bool TAIL_SPILLS = false;
+  constexpr bool TAIL = SPLIT && !TD && !GEN && NXW == NXP_MAX && !TAIL_SPILLS && tail_shape(KIND, H, L, ACT);
+  // this workgroup's index in the launch's unit map (dpi_tail_units.h): the grid index, past the
+  // first units of a launch of its own (a.unit0, the two-launch form of the tests)
+  unsigned gidx = blockIdx.x;
+  if constexpr (TAIL) gidx += a.unit0;
   if constexpr (FBC) {
     static_assert(sizeof(BaseLds<NTH>) <= sizeof(SH), "base blocks overlay the path LDS");
-    if ((int)blockIdx.x < fb.nbase) {
-      base_point<KIND, ZERO, NTH, false>(e, net, a.tx, blockIdx.x, const_cast<float*>(a.gx), const_cast<float*>(a.fb),
+    if ((int)gidx < fb.nbase) {
+      base_point<KIND, ZERO, NTH, false>(e, net, a.tx, gidx, const_cast<float*>(a.gx), const_cast<float*>(a.fb),
                                   const_cast<float*>(a.bx), fb.rec, fb.smp, a.tickets,
                                   *reinterpret_cast<BaseLds<NTH>*>(&sh));
-      base_publish(fb, blockIdx.x);
+      base_publish(fb, gidx);
       return;
     }
   }
-  const unsigned bid = GEN ? gbid : blockIdx.x - (FB ? (unsigned)fb.nbase : 0u);
+  unsigned bid = GEN ? gbid : gidx - (FB ? (unsigned)fb.nbase : 0u);
+  [[maybe_unused]] int role = TAIL_WHOLE;  // TAIL_T / TAIL_I: a unit of one of the call's last a.tail blocks
+  if constexpr (TAIL) {
+    if (a.tail) {
+      const TailUnit un = tail_unit(gidx, FB ? fb.nbase : 0, a.n * a.nbp, a.tail, a.tail_order);
+      role = un.role;
+      bid = (unsigned)un.bid;
+    }
+  }
   const int i = bid / a.nbp;
   const int blk = bid - i * a.nbp;
   // independent Philox chains per wave in the noise loops (2 vs 1: 2 % on the one- and two-wave-per-SIMD
@@ -2333,6 +2396,11 @@ __device__ __forceinline__ void paths_body(const EqDev& e, const NET& net, const
   //    fp32: every staged chunk is the ring's first 17 KB (32 rows of stride WST), slot 1's end is free.
   //    No barrier is added (one between the integrand and the terminal rollout measured 2 us slower
   //    per launch).
+  // Tail units (TAIL): a T-unit builds tables and never touches the ring — it runs no MLP, and as a
+  // finisher it copies the hand-over into sh.S / sh.bsh, not into the ring, after the join's barriers.
+  // An I-unit is the terminal-last order's prefix (integral rollout, the barrier after base_poll_, the
+  // MLP) and builds no table after the MLP: as a finisher it reloads the terminal sums as a parked
+  // block does.  Neither adds a hazard to the two above.
   // One instance keeps the plain form: the split OU 4 x 128 ELU k_paths, at 255 registers without the
   // table, spills 6 VGPRs at 256 with it (and its occupancy is not lowered to make it fit).  For the
   // same reason it parks nothing (PARK_SPILLS below: one VGPR spilled with the park's stores and
@@ -2659,6 +2727,17 @@ __device__ __forceinline__ void paths_body(const EqDev& e, const NET& net, const
   // (NOISE_TAB_SPILLS' instance, at 255 registers, spills one with the park too: all terminal-last)
   constexpr bool PARK_SPILLS = NOISE_TAB_SPILLS;
   constexpr bool PARK = SPLIT && !GBM && !TD && !GEN && NXW == NXP_MAX && !PARK_SPILLS;
+  static_assert(TAIL == (PARK && !TAIL_SPILLS), "the tail units: the parking instances");
+  // Tail units (dpi_tail_units.h): with a.tail the last a.tail blocks of the call run
+  // as two workgroups each, so that a slot which falls idle in the launch's last round takes a share
+  // of a block.  What the parked order made possible: the terminal rollout leaves nothing behind but
+  // ST (the park row) and the per-wave g statistics, and the integral half nothing but the noise tile
+  // S and bsh.  The T-unit rolls out the terminal noise and stores ST and its gst; the I-unit runs
+  // integral rollout and MLP and stores S (the park's 16-B form, by dim-block) and bsh to the block's
+  // extra rows.  Each then joins (tail_join): the first to arrive leaves, the second — whichever it
+  // is — loads the other's half (ST and gst into the lanes that stored them, the tile and bsh into
+  // LDS) and runs phase 3, alone counting on the point's tickets.  Same counters, same sums, the gst rows added in terminal_sum's
+  // order from LDS: the bits of the whole block.
   bool tlast = false;
   if constexpr (TD) {
     tlast = false;  // the terminal MLP needs the noise tile before the integral rollout
@@ -2762,6 +2841,56 @@ __device__ __forceinline__ void paths_body(const EqDev& e, const NET& net, const
       ST[c][3] = v[3];
     }
   };
+  // Tail units: a split block's extra rows (dpi_tail_units.h).  ng: the g statistics that are not +0
+  // for every path (Eq<KIND>::gstat), the only ones handed over.
+  [[maybe_unused]] const int ng = KIND == DPI_EQ_CHA ? 1 : e.ncomp;
+  [[maybe_unused]] auto xrow = [&]() -> float* {
+    return a.park + (size_t)tail_xrow(a.n * a.nbp, a.tail, (int)bid, nb, ng) * PARK_ROW;
+  };
+  [[maybe_unused]] auto xjoin = [&]() -> unsigned long long* {
+    return reinterpret_cast<unsigned long long*>(xrow() + tail_off_join(nb, ng));
+  };
+  // T-unit -> I-finisher: this wave's statistics, [c][wave][lane], taken back by the same lane
+  [[maybe_unused]] auto gst_store = [&]() {
+    float* const g = xrow() + tail_off_gst(nb) + wv * P + lane;
+#pragma unroll
+    for (int c = 0; c < NSG; ++c)
+      if (c < ng) g[c * 4 * P] = gst[c];
+  };
+  [[maybe_unused]] auto gst_load = [&]() {
+    const float* const g = xrow() + tail_off_gst(nb) + wv * P + lane;
+#pragma unroll
+    for (int c = 0; c < NSG; ++c) gst[c] = c < ng ? g[c * 4 * P] : 0.f;
+  };
+  // I-unit -> T-finisher: the noise tile by dim-block (lane = path, 16 B, as a park row) — each wave the
+  // dim-blocks it rolled out, read back from its own LDS writes — and bsh from the lanes that wrote it
+  [[maybe_unused]] auto tile_store = [&]() {
+    floatx4* const xs = reinterpret_cast<floatx4*>(xrow()) + lane;
+#pragma unroll
+    for (int c = 0; c < NBW; ++c) {
+      const int j = (3 - wv) + 4 * c;
+      if (j < nb)
+        xs[64 * j] = floatx4{sh.S[(4 * j) * SS + lane], sh.S[(4 * j + 1) * SS + lane], sh.S[(4 * j + 2) * SS + lane],
+                             sh.S[(4 * j + 3) * SS + lane]};
+    }
+  };
+  [[maybe_unused]] auto bsh_store = [&]() {
+    const int pp = 16 * wv + (lane & 15);
+    if ((lane >> 4) == 0) xrow()[tail_off_bsh(nb, ng) + pp] = sh.bsh[pp];
+  };
+  [[maybe_unused]] auto tile_load = [&]() {
+    const floatx4* const xs = reinterpret_cast<const floatx4*>(xrow()) + lane;
+#pragma unroll
+    for (int c = 0; c < NBW; ++c) {
+      const int j = wv + 4 * c;
+      if (j < nb) {
+        const floatx4 v = xs[64 * j];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) sh.S[(4 * j + q) * SS + lane] = v[q];
+      }
+    }
+    if (wv == 0) sh.bsh[lane] = xrow()[tail_off_bsh(nb, ng) + lane];
+  };
   // DPI_PHASE_STAMPS: lane 0 of every wave stores the clock at phase boundary k to the park row's
   // last dim-block of wave 0, which no wave parks at nx <= 112 (the stamps are off above that):
   // 64-bit words [0] HW_ID | XCC_ID << 32, [1] the order, [4 + 8 wave + k] the stamps.
@@ -2773,14 +2902,17 @@ __device__ __forceinline__ void paths_body(const EqDev& e, const NET& net, const
         __builtin_amdgcn_sched_barrier(0);
         asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(tk)::"memory");
         __builtin_amdgcn_sched_barrier(0);
-        unsigned long long* const sp =
-            reinterpret_cast<unsigned long long*>(a.park + (size_t)bid * PARK_ROW + (NBW - 1) * 64 * 4);
+        // (an I-unit: the same dim-block of wave 1, as free as wave 0's, so the two units of a block
+        // stamp apart; word [1] carries the role in bits 8.., and a unit that is not the finisher
+        // leaves stamps 5-7 unwritten)
+        unsigned long long* const sp = reinterpret_cast<unsigned long long*>(
+            a.park + (size_t)bid * PARK_ROW + ((role == TAIL_I ? NBW : 0) + NBW - 1) * 64 * 4);
         if (lane == 0) {
           sp[4 + 8 * wv + k] = tk;
           if (k == 0 && wv == 0) {
             sp[0] = (unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 4) |
                     ((unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 20) << 32);  // HW_ID, XCC_ID
-            sp[1] = tlast ? 1ull : 0ull;
+            sp[1] = (tlast ? 1ull : 0ull) | ((unsigned long long)role << 8);
           }
         }
       }
@@ -2801,28 +2933,50 @@ __device__ __forceinline__ void paths_body(const EqDev& e, const NET& net, const
     __syncthreads();
   } else if constexpr (PARK) {
     stamp(0);
-    if (!tlast) {
+    if (TAIL && role == TAIL_T) {  // an early-leaving role, as the base blocks are
       terminal_rollout();
       park_store();
-      terminal_publish();
+      gst_store();
       stamp(1);
-    }
-    integral_rollout();
-    stamp(2);
-    base_poll_();
-    __syncthreads();
-    base_load();
-    stamp(3);
-    integrand();
-    stamp(4);
-    if (tlast) {
-      terminal_rollout();
+      if (!tail_join(xjoin(), a.tail_seq)) return;
+      // T-finisher: the point's record, the I-unit's noise tile and bsh, then phase 3 below
+      base_poll_();
+      __syncthreads();
+      base_load();
       terminal_publish();
+      tile_load();
     } else {
-      park_load();
+      if (!tlast && role == TAIL_WHOLE) {
+        terminal_rollout();
+        park_store();
+        terminal_publish();
+        stamp(1);
+      }
+      integral_rollout();
+      if (TAIL && role == TAIL_I) tile_store();
+      stamp(2);
+      base_poll_();
+      __syncthreads();
+      base_load();
+      stamp(3);
+      integrand();
+      stamp(4);
+      if (TAIL && role == TAIL_I) {
+        bsh_store();
+        if (!tail_join(xjoin(), a.tail_seq)) return;
+        // I-finisher: the T-unit's sums, as a parked block reloads its own
+        park_load();
+        gst_load();
+        terminal_publish();
+      } else if (tlast) {
+        terminal_rollout();
+        terminal_publish();
+      } else {
+        park_load();
+      }
     }
     stamp(5);
-    ap = terminal_sum();  // its barrier also publishes bsh
+    ap = terminal_sum();  // its barrier also publishes bsh (a T-finisher: the tile it copied, too)
     stamp(6);
   } else if (!tlast) {
     terminal_rollout();

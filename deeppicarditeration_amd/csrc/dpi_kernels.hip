@@ -1162,6 +1162,81 @@ static bool fused_reduce_on() { return env_int("DPI_FUSED_REDUCE", 1) != 0; }
 // DPI_PARK_MAX_BLOCKS path blocks, OU 4 x 128 ELU) run terminal-last whatever it says.
 static int path_order() { return env_int("DPI_ORDER", 0); }
 
+// Tail units (dpi_tail_units.h, dpi_device.h paths_body): how many of a parking launch's last path
+// blocks run as a T-unit and an I-unit.  Read per call.  DPI_TAIL: 0 whole blocks (the launch before
+// the units), a count (capped by the park rows the call leaves free, tail_cap), unset: the default
+// rule.  DPI_TAIL_ORDER: the split part as I-units then T-units (0, the default) or T-units then
+// I-units (1).  DPI_TAIL_LAUNCHES=2 (tests): the second units as a launch of their own behind the
+// first on the call's stream, so stream order decides which unit finishes — order 0 the T-units,
+// order 1 the I-units.
+// The default rule (the sweeps under profiles/tail_split_ab): three quarters of the
+// device's resident workgroup slots (2 per CU: 384 of 512 on MI355X), or all the call's blocks if that
+// is fewer, within the cap; a multiple of 8 where it reaches 8, so that both units of a block go to one
+// XCD.  Measured on k_paths at 256 / 512 / 1,024 / 1,536 blocks (rounds_k_paths.txt, the rule against
+// whole blocks): -14.3 / -0.8 / -1.5 / -1.1 %; splitting a quarter of the slots or fewer is slower than not splitting (the units then
+// only lengthen the last round), and at 1,024 blocks so is splitting 640 and more.
+static int tail_default(int slots, int cap) {
+  const int t = std::min(cap, 3 * slots / 4);
+  return t >= 8 ? t & ~7 : t;
+}
+static bool tail_two_launches() { return env_int("DPI_TAIL_LAUNCHES", 1) == 2; }
+// Hand-off sequence numbers: one per fused launch or launch with tail units, process-wide, never 0,
+// so a hand-off or join word left in a workspace by an earlier launch (or never written) does not
+// match this launch's.
+static std::atomic<uint32_t> g_ready_seq{0};
+static uint32_t next_ready_seq() {
+  uint32_t s;
+  do s = g_ready_seq.fetch_add(1, std::memory_order_relaxed) + 1u;
+  while (s == 0u);
+  return s;
+}
+// Sets a.tail / a.tail_order / a.tail_seq of a k_paths or k_paths_fb launch.  Units run only where the
+// kernel instance has them (tail_shape, no TD), the call has a park and asks for both estimators.
+static void arm_tail(PathArgs& a, dpi_problem p, dpi_net net, const WsLayout& w) {
+  a.tail = 0;
+  if (!a.park || a.flags != DPI_BOTH || p->td_dt > 0.f || net->d.kind != 1 ||
+      !tail_shape(p->e.kind, net->d.H, net->d.L, net->d.act))
+    return;
+  const int nblk = a.n * a.nbp, nb = (p->e.nx + 3) >> 2, ng = p->e.kind == DPI_EQ_CHA ? 1 : p->e.ncomp;
+  const int cap = tail_cap(nblk, (long long)w.park_rows, nb, ng);
+  const char* env = std::getenv("DPI_TAIL");
+  const int want = env ? std::atoi(env) : tail_default(2 * cu_count(), cap);
+  a.tail = std::max(0, std::min(want, cap));
+  if (!a.tail) return;
+  a.tail_order = env_int("DPI_TAIL_ORDER", 0) != 0;
+  a.tail_seq = next_ready_seq();
+}
+// A path launch with its units: one launch over [base][whole][first units][second units], or
+// (tail_two_launches) the second units behind it as a launch of their own, offset in the unit map as
+// k_paths_gen's ranges are in the block list.
+// What dpi_launch_units reports: the calling thread's last k_paths / k_paths_fb launch.
+static thread_local int g_units_tail = 0, g_units_grid = 0, g_units_launches = 0;
+static bool dispatch_units(const dpi_problem_s* p, const dpi_net_s* net, Launch q, const PathArgs& a, int nbase) {
+  const int nblk = a.n * a.nbp;
+  q.a = &a;
+  q.nblocks = (int)tail_grid(nbase, nblk, a.tail);
+  g_units_tail = a.tail;
+  g_units_grid = q.nblocks;
+  g_units_launches = a.tail && tail_two_launches() ? 2 : 1;
+  if (!a.tail || !tail_two_launches()) return dispatch_any(p, net, q);
+  q.nblocks -= a.tail;
+  if (!dispatch_any(p, net, q)) return false;
+  PathArgs a2 = a;
+  a2.unit0 = tail_first(nbase, nblk, a.tail, 1);
+  q.a = &a2;
+  q.nblocks = a.tail;
+  q.t0 = q.t1 = nullptr;
+  return dispatch_any(p, net, q);
+}
+
+int dpi_launch_units(int* tail, int* grid, int* launches) {
+  if (!tail || !grid || !launches) return fail(DPI_ERR_ARG, "launch_units: null argument");
+  *tail = g_units_tail;
+  *grid = g_units_grid;
+  *launches = g_units_launches;
+  return 0;
+}
+
 static size_t hess_extra(int n, int M, int nx, size_t* moff);
 // Validates a label-moments call and fills its PathArgs (shared by dpi_label_moments,
 // dpi_label_prepare and, with `hess`, the Hessian-label calls: GBM with MLP or zero nets only, their
@@ -1277,7 +1352,8 @@ static int moments_impl(dpi_problem p, dpi_net net, const float* tx, int n, int 
                                  "was enqueued on this workspace (the fused reduce's tickets are zeroed there)");
       arm_fused_reduce(a, net, ws, w, M, flags, moments, y, bound);
     }
-    if (!dispatch_any(p, net, q))
+    arm_tail(a, p, net, w);
+    if (!dispatch_units(p, net, q, a, 0))
       return fail(DPI_ERR_UNSUPPORTED, "label_moments: unsupported equation/network shape");
     if (a.tickets) {
       HIPCHK(hipGetLastError());
@@ -1303,16 +1379,6 @@ static bool fused_base_ok(dpi_problem p, dpi_net net) {
   if (net->d.kind == 0) return fused_base_shape(p->e.kind, 0, 0, true, DPI_ACT_ELU);
   return net->d.kind == 1 && mlp_split(net) && fused_base_shape(p->e.kind, net->d.H, net->d.L, false, net->d.act);
 }
-// Hand-off sequence numbers: one per fused launch, process-wide, never 0, so a hand-off word left
-// in a workspace by an earlier launch (or never written) does not match this launch's.
-static std::atomic<uint32_t> g_ready_seq{0};
-static uint32_t next_ready_seq() {
-  uint32_t s;
-  do s = g_ready_seq.fetch_add(1, std::memory_order_relaxed) + 1u;
-  while (s == 0u);
-  return s;
-}
-
 // sample_with_gradients (picard/data.py:211-223) as one call.  First-order Cha / OU labels of MLP
 // and zero nets (no TD; <= 64 path blocks per point, so the label reduce runs in the path launch):
 // ONE k_paths launch of n base blocks (base_point: the point's draws 1-3, g(x), f_b, bx; published
@@ -1355,7 +1421,8 @@ int dpi_sample_with_gradients(dpi_problem p, dpi_net net, int n, int M, int K, u
     Launch q = path_launch(a, n + n * a.nbp, (hipStream_t)stream);
     q.fbase = &fb;
     take_timer(q.t0, q.t1);
-    if (!dispatch_any(p, net, q))
+    arm_tail(a, p, net, wl);
+    if (!dispatch_units(p, net, q, a, n))
       return fail(DPI_ERR_UNSUPPORTED, "sample_with_gradients: unsupported equation/network shape");
     HIPCHK(hipGetLastError());
     base_tag_set(ws, n);  // the base blocks zeroed the tickets and left the baseline in ws

@@ -248,6 +248,11 @@ int dpi_build_id(char* buf, size_t len);
 #define DPI_LAUNCH_TIMERS 256
 int dpi_launch_timer_arm(int slot);
 int dpi_launch_timer_ms(int slot, float* ms);
+/* What the calling thread's last k_paths / k_paths_fb launch (a label call's path launch) was made
+ * of: *tail the path blocks it ran as two units (DESIGN.md §2.2 "tail units"; 0: whole blocks),
+ * *grid its workgroups (base blocks + path blocks + *tail), *launches 1, or 2 in the tests' form that
+ * issues the second units as a launch of their own.  Host state only; zeros before the first launch. */
+int dpi_launch_units(int* tail, int* grid, int* launches);
 
 /* Device workspace a dpi_* call on (p, net, n points, M paths) needs.
  * Cha / OU problems (nx <= 128) with an MLP net of any shape add the park as the last region (the

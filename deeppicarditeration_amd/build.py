@@ -1,7 +1,7 @@
 """Build libdpi_hip.so in-tree for gfx950 (hipcc cross-compiles without a GPU).
 
 The translation units of `UNITS` (the C-ABI / PIS / reduce TU, the network-handle TU, and one
-`dpi_paths_*.hip` per row of the unit table in `csrc/dpi_dispatch.h`) compile in parallel, at most
+`dpi_paths_*.hip` per row of the unit table in `csrc/dpi_route.h`) compile in parallel, at most
 `MAX_JOBS` at once, to objects, then link into one
 shared library together with a generated one-function unit, `dpi_build_id()`, that returns the
 SHA-256 of the sources and flags (`source_hash`).  A build is current when the library itself
@@ -19,21 +19,19 @@ from pathlib import Path
 ROOT = Path(__file__).resolve().parent
 REPO = ROOT.parent
 CSRC = ROOT / "csrc"
-UNITS = ["dpi_kernels.hip", "dpi_net.hip", "dpi_paths_cha.hip", "dpi_paths_ou.hip", "dpi_paths_gbm.hip", "dpi_paths_td_cha.hip",
-         "dpi_paths_td_ou.hip", "dpi_paths_td_gbm.hip", "dpi_paths_cha_tanh.hip", "dpi_paths_ou_tanh.hip",
-         "dpi_paths_gbm_tanh.hip", "dpi_paths_td_cha_tanh.hip", "dpi_paths_td_ou_tanh.hip", "dpi_paths_td_gbm_tanh.hip",
-         "dpi_paths_fb_cha.hip", "dpi_paths_fb_ou.hip", "dpi_paths_wide_cha.hip", "dpi_paths_wide_ou.hip",
-         "dpi_paths_wide_cha_tanh.hip", "dpi_paths_wide_ou_tanh.hip", "dpi_paths_wide_gbm.hip",
-         "dpi_paths_wide_gbm_tanh.hip", "dpi_paths_gen_cha.hip", "dpi_paths_gen_ou.hip", "dpi_paths_gen_cha_tanh.hip",
-         "dpi_paths_gen_ou_tanh.hip", "dpi_paths_gen_gbm.hip", "dpi_paths_gen_gbm_tanh.hip", "dpi_paths_head_cha_128.hip", "dpi_paths_head_cha_256.hip",
-         "dpi_paths_head_ou_128.hip", "dpi_paths_head_ou_256.hip", "dpi_paths_head_cha_128_tanh.hip",
-         "dpi_paths_head_cha_256_tanh.hip", "dpi_paths_head_ou_128_tanh.hip", "dpi_paths_head_ou_256_tanh.hip",
-         "dpi_paths_head_base_cha.hip", "dpi_paths_head_base_ou.hip", "dpi_paths_term_cha.hip", "dpi_paths_term_ou.hip",
-         "dpi_paths_term_cha_tanh.hip", "dpi_paths_term_ou_tanh.hip", "dpi_paths_term_head_cha_128.hip",
-         "dpi_paths_term_head_cha_256.hip", "dpi_paths_term_head_ou_128.hip", "dpi_paths_term_head_ou_256.hip",
-         "dpi_paths_term_head_cha_128_tanh.hip", "dpi_paths_term_head_cha_256_tanh.hip",
-         "dpi_paths_term_head_ou_128_tanh.hip", "dpi_paths_term_head_ou_256_tanh.hip",
-         "dpi_paths_term_head_base_cha.hip", "dpi_paths_term_head_base_ou.hip"]
+def unit_files():
+    """dpi_kernels.hip, dpi_net.hip and one dpi_paths_<NAME>.hip per row X(NAME, ...) of DPI_UNITS
+    (csrc/dpi_route.h); a row without its file, or such a file without a row, is an error."""
+    import re
+    rows = re.findall(r"^\s*X\((\w+),", (CSRC / "dpi_route.h").read_text(), flags=re.M)
+    want = [f"dpi_paths_{r}.hip" for r in rows]
+    odd = sorted(set(want) ^ {f.name for f in CSRC.glob("dpi_paths_*.hip")})
+    if odd:
+        raise RuntimeError(f"DPI_UNITS and csrc/dpi_paths_*.hip disagree on {', '.join(odd)}")
+    return ["dpi_kernels.hip", "dpi_net.hip", *want]
+
+
+UNITS = unit_files()
 OBJ = ROOT / "build"
 OUT = ROOT / "libdpi_hip.so"
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

@@ -1,6 +1,6 @@
 // The general MLP family of the first-order path kernel (Cha / OU, nx <= 128): any construct_mlp value
 // network of 1..GEN_LMAX hidden layers, each 1..GEN_HMAX wide, all-ELU or all-Tanh, that has no
-// specialised k_paths instance (dpi_dispatch.h spec_shape).  Included by dpi_device.h.
+// specialised k_paths instance (dpi_route.h spec_shape).  Included by dpi_device.h.
 //
 // The specialised mlp_tile keeps every layer's activations in registers (L x H/16 x 4 per lane), which
 // ends at 4 x 128.  Here the layer count is a run-time loop and registers hold two layers only — the

@@ -1,6 +1,6 @@
 // The general MLP family for GBM (GBMEquationComplexExact, nx <= 128): any construct_mlp value network of
 // 1..GEN_LMAX hidden layers, each 1..GG_H = 64 wide, all-ELU or all-Tanh, that has no specialised GBM
-// k_paths instance (dpi_dispatch.h DPI_SHAPES_GBM).  Included by dpi_device.h after dpi_general.h.
+// k_paths instance (dpi_route.h DPI_SHAPES_GBM).  Included by dpi_device.h after dpi_general.h.
 //
 // The net is read from the NetGen image of width cap 128 that the upload already builds (row stride
 // net.H = 128, ht = 2 or 4 tiles in use); nothing is uploaded twice.

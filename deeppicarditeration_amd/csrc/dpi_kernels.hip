@@ -1,7 +1,7 @@
 // C-ABI of include/dpi.h (libdpi_hip.so): problem handles, workspace layout, routing, the
 // PISGradNet pipeline host code, the label calls, reduce and finalize kernels.  The network handles
 // and their device images: dpi_net.hip, dpi_net_image.h.  Device code: dpi_device.h; the k_paths /
-// k_baseline instantiations: one dpi_paths_*.hip unit per row of dpi_dispatch.h's unit table.
+// k_baseline instantiations: one dpi_paths_*.hip unit per row of dpi_route.h's unit table.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -459,7 +459,7 @@ static bool gbm_noise_prep(dpi_problem p, dpi_net net) {
   static const bool on = env_int("DPI_GBM_PREP", 1) != 0;
   return on && p && net && net->d.kind == 1 && p->e.kind == DPI_EQ_GBM;
 }
-// park: the pair runs a parking path kernel (park_pair): DPI_PARK_MAX_BLOCKS rows of PARK_ROW floats,
+// park: the pair's workspace holds the park (Route::park): DPI_PARK_MAX_BLOCKS rows of PARK_ROW floats,
 // one per path block of a call, in which a terminal-first block keeps its terminal sums across the
 // MLP (dpi_device.h paths_body).  A constant, so the workspace stays affine in n and M; a call with
 // more path blocks than rows leaves it unused and runs every block terminal-last.
@@ -807,111 +807,35 @@ extern "C" int dpi_sample_points_t(dpi_problem p, int n, uint64_t seed, uint32_t
   return 0;
 }
 
-// Which k_paths family serves a (problem, net) pair: a pair with a specialised instance keeps it; any
-// other MLP net within the general family's caps runs that (it holds the general image then).
-static bool runs_general(const dpi_problem_s* p, const dpi_net_s* net) {
-  return net->d.kind == 1 && net->gen && !(net->spec && spec_shape(p->e.kind, net->d.H, net->d.L));
+// The route of a pair for one kind of call (dpi_route.h), in the net's effective GEMM mode.
+static Route pair_route(dpi_problem p, dpi_net net, RouteCall call) {
+  return route(route_pair(p, net, p->td_dt > 0.f, mlp_split(net)), call);
 }
-// The pairs whose workspace holds the park (dpi_device.h paths_body PARK): first-order Cha / OU labels
-// at nx <= 128 of any MLP net.  By problem and network kind only, not by the kernel family or instance
-// that ends up running: the workspace size does not move with the precision mode, ESTIMATE_DELTA_T or
-// the net's widths (a caller may set the first two after sizing it), and the workspaces of the
-// specialised and the general family keep differing by the general family's stash alone.  The kernels
-// that park are the fp16-split specialised instances (not OU 4 x 128 ELU, PARK_SPILLS); every other
-// launch leaves the region unused.
-static bool park_pair(dpi_problem p, dpi_net net) {
-  return p && net && net->d.kind == 1 && p->e.kind != DPI_EQ_GBM && p->e.nx <= NXP_MAX;
+static int refuse(const Route& r) { return fail(r.code, std::string(r.pre) + r.msg); }
+// ... behind the null check of every entry point; refuses what is due before the call's own arguments
+// are looked at (a late refusal stays in *r: label_args returns it once they have passed).
+static int route_call(dpi_problem p, dpi_net net, RouteCall call, Route* r) {
+  if (!p || !net) return fail(DPI_ERR_ARG, "null problem or net");
+  *r = pair_route(p, net, call);
+  return r->code && r->stage != ROUTE_LATE ? refuse(*r) : 0;
 }
-// The general family's refusals, each naming its cap.  td: the call uses the TD estimators.
-static int general_refusal(const dpi_problem_s* p, const dpi_net_s* net, bool td, bool hess) {
-  if (net->term) {  // a terminal-enforcing net: the general family whatever its widths
-    const char* pre = "a terminal-enforcing network (PicardSolutionEnforceTerminal) runs the general MLP family, which ";
-    if (p->e.kind == DPI_EQ_GBM)
-      return fail(DPI_ERR_UNSUPPORTED, std::string(pre) + "serves Cha and OU problems only: GBM has no terminal-enforcing "
-                                                          "instance");
-    if (hess) return fail(DPI_ERR_UNSUPPORTED, std::string(pre) + "has no Hessian labels");
-    if (p->e.nx > NXP_MAX)
-      return fail(DPI_ERR_UNSUPPORTED, std::string(pre) + "is compiled for nx <= 128 (NXP_MAX)");
-    if (td)
-      return fail(DPI_ERR_UNSUPPORTED, std::string(pre) + "has no TD estimators (ESTIMATE_DELTA_T > 0)");
-    return 0;
-  }
-  if (net->head) {  // a gradient head: the general family whatever its widths
-    const char* pre = "a ValueGradient / OnlyGradient network (a gradient head) runs the general MLP family, which ";
-    if (p->e.kind == DPI_EQ_GBM)
-      return fail(DPI_ERR_UNSUPPORTED, std::string(pre) + "serves Cha and OU problems only: GBM needs the Hessian of u, "
-                                                          "which a gradient head does not give");
-    if (hess) return fail(DPI_ERR_UNSUPPORTED, std::string(pre) + "has no Hessian labels");
-    if (p->e.nx > NXP_MAX)
-      return fail(DPI_ERR_UNSUPPORTED, std::string(pre) + "is compiled for nx <= 128 (NXP_MAX)");
-    if (td)
-      return fail(DPI_ERR_UNSUPPORTED, std::string(pre) + "has no TD estimators (ESTIMATE_DELTA_T > 0)");
-    return 0;
-  }
-  const char* pre = "this network has no specialised kernel instance and the general MLP family (up to 8 hidden "
-                    "layers of width 256) ";
-  if (p->e.kind == DPI_EQ_GBM) {  // dpi_general_gbm.h: the width-128 image with at most 4 tiles in use
-    if (net->g.H != 128 || net->g.ht > GG_H / 16 || net->g.L > GEN_LMAX)
-      return fail(DPI_ERR_UNSUPPORTED, std::string(pre) + "serves GBM problems for hidden widths <= 64 only (up to 8 hidden "
-                                                          "layers): GBM keeps W1x and the tangents of every layer on chip");
-    const char* pg = "this GBM network has no specialised kernel instance and the general MLP family on GBM (up to 8 hidden "
-                     "layers of width 64) ";
-    if (hess) return fail(DPI_ERR_UNSUPPORTED, std::string(pg) + "has no Hessian labels (nor SUPERVISE_HESSIAN)");
-    if (p->e.nx > NXP_MAX) return fail(DPI_ERR_UNSUPPORTED, std::string(pg) + "is compiled for nx <= 128 (NXP_MAX)");
-    if (td) return fail(DPI_ERR_UNSUPPORTED, std::string(pg) + "has no TD estimators (ESTIMATE_DELTA_T > 0)");
-    return 0;
-  }
-  if (hess) return fail(DPI_ERR_UNSUPPORTED, std::string(pre) + "has no Hessian labels");
-  if (p->e.nx > NXP_MAX)
-    return fail(DPI_ERR_UNSUPPORTED, std::string(pre) + "is compiled for nx <= 128 (NXP_MAX)");
-  if (td)
-    return fail(DPI_ERR_UNSUPPORTED, std::string(pre) + "has no TD estimators (ESTIMATE_DELTA_T > 0): those need at most "
-                                                        "4 hidden layers of width 128");
-  return 0;
-}
+static bool park_pair(dpi_problem p, dpi_net net) { return p && net && pair_route(p, net, ROUTE_PATHS).park; }
 
-// A GBM MLP pair that neither family serves: some hidden layer is wider than 64 (a net of 2-4 layers up to
-// 128 wide holds the specialised image only, so runs_general does not see it).
-static bool gbm_too_wide(const dpi_problem_s* p, const dpi_net_s* net) {
-  return p->e.kind == DPI_EQ_GBM && net->d.kind == 1 && !runs_general(p, net) &&
-         !(net->spec && spec_shape(DPI_EQ_GBM, net->d.H, net->d.L));
-}
-static int gbm_too_wide_refusal() {
-  return fail(DPI_ERR_UNSUPPORTED, "GBM networks need every hidden layer <= 64 wide (up to 8 hidden layers): GBM keeps W1x "
-                                   "and the tangents of every layer on chip");
-}
-
-static bool dispatch_any(const dpi_problem_s* p, const dpi_net_s* net, const Launch& q) {
-  if (q.gen) {  // the general MLP family (check_pair refused what it does not serve)
-    const bool tanh_g = !q.baseline && net->g.act == DPI_ACT_TANH;
-    // head nets: the baseline unit, or the path unit of the image's width cap
-    const int head = !q.head ? 0 : q.baseline ? HEAD_BASE : net->g.H;
-    for (const Unit& u : UNITS)
-      if (u.is(p->e.kind, false, tanh_g ? DPI_ACT_TANH : DPI_ACT_ELU, false, NXP_MAX, true, head, q.term))
-        return u.dispatch(p, net, q);
-    return false;
-  }
-  // The unit's key (dpi_dispatch.h DPI_UNITS).  k_paths_fb (fused_base_ok) has ELU, non-TD, narrow
-  // rows only, and GBM has none.  The baseline is shape- and activation-generic: it lives in the
-  // plain ELU units whatever the net's activation, the problem's width or TD mode.  The wide
-  // first-order units (nx <= NXW_MAX) have no TD or Hessian forms.
-  const bool fb = q.fbase != nullptr, paths = !q.baseline && !fb;
-  const bool td = paths && q.td && !q.hess;
-  const bool wide = paths && p->e.nx > NXP_MAX;
-  if (wide && (td || q.hess)) return false;
-  const bool tanh = paths && net->d.kind == 1 && net->d.act == DPI_ACT_TANH;
-  const int act = tanh ? DPI_ACT_TANH : DPI_ACT_ELU, nxw = wide ? NXW_MAX : NXP_MAX;
-  for (const Unit& u : UNITS)
-    if (u.is(p->e.kind, td, act, fb, nxw)) return u.dispatch(p, net, q);
-  return false;  // no such unit: GBM has no fused baseline
+// The launch of the route's unit.  A unit that cannot serve the call it was chosen for is a bug in the
+// route: reported here, for every entry point.
+static int launch_unit(const dpi_problem_s* p, const dpi_net_s* net, const Launch& q) {
+  if (q.unit < N_UNITS && UNIT_FNS[q.unit](p, net, q)) return 0;
+  return fail(DPI_ERR_UNSUPPORTED, std::string("internal error: the route chose a unit that holds no kernel for the call (") +
+                                       (q.unit < N_UNITS ? UNIT_NAMES[q.unit] : "none") + ")");
 }
 
 // The two kinds of Launch.  The per-point baseline of n points writes the workspace's gx / fb / bx /
 // hb regions and zeroes the fused reduce's tickets; a path launch (k_paths, k_paths_fb) runs nblocks
 // workgroups over a's paths.
-static Launch baseline_launch(const float* tx, int n, void* ws, const WsLayout& w, hipStream_t st) {
+static Launch baseline_launch(const Route& r, const float* tx, int n, void* ws, const WsLayout& w, hipStream_t st) {
   char* b = (char*)ws;
   Launch q;
+  q.unit = r.unit;
   q.baseline = true;
   q.tx = tx;
   q.n = n;
@@ -923,51 +847,24 @@ static Launch baseline_launch(const float* tx, int n, void* ws, const WsLayout& 
   q.st = st;
   return q;
 }
-// Routes a Launch of the pair to the general family where runs_general holds (path launches: with the
-// workspace's stash).
-static void route_launch(Launch& q, dpi_problem p, dpi_net net, void* ws, const WsLayout& w) {
-  q.gen = runs_general(p, net);
-  q.head = q.gen && net->head;
-  q.term = q.gen && net->term;
-  if (q.gen && !q.baseline && !q.head) q.stash = (floatx4*)((char*)ws + w.stash);
-}
-static Launch path_launch(const PathArgs& a, int nblocks, hipStream_t st) {
+static Launch path_launch(const Route& r, const PathArgs& a, int nblocks, void* ws, const WsLayout& w, hipStream_t st) {
   Launch q;
+  q.unit = r.unit;
   q.a = &a;
   q.nblocks = nblocks;
   q.st = st;
+  if (r.stash) q.stash = (floatx4*)((char*)ws + w.stash);
   return q;
 }
 
-static int check_pair(dpi_problem p, dpi_net net);
 extern "C" {
-static int check_pair(dpi_problem p, dpi_net net) {
-  if (!p || !net) return fail(DPI_ERR_ARG, "null problem or net");
-  if (net->d.kind && net->n_in != 1 + p->e.nx) return fail(DPI_ERR_ARG, "net input width != 1 + nx");
-  if (net->d.kind && net->d.nxp > NXW_MAX) return fail(DPI_ERR_ARG, "nx too large");
-  if (p->e.nx > NXP_MAX && net->d.kind == 2)
-    return fail(DPI_ERR_UNSUPPORTED, "PISGradNet: nx exceeds the compiled maximum state dimension 128 (NXP_MAX)");
-  if (runs_general(p, net)) {
-    if (int rc = general_refusal(p, net, p->td_dt > 0.f, false)) return rc;
-  }
-  if (gbm_too_wide(p, net)) return gbm_too_wide_refusal();
-  if (net->term && net->term_T != p->e.T)
-    return fail(DPI_ERR_ARG, "the terminal-enforcing net was built for another T than the problem's");
-  return 0;
-}
-
+// The family question alone (ROUTE_FAMILY), with the caller's td.
 int dpi_pair_family(dpi_problem p, dpi_net net, int td, int* family) {
   if (!p || !net || !family) return fail(DPI_ERR_ARG, "pair_family: null problem, net or family");
-  if (net->d.kind && net->n_in != 1 + p->e.nx) return fail(DPI_ERR_ARG, "net input width != 1 + nx");
-  *family = DPI_FAMILY_SPECIALISED;
-  if (net->d.kind != 1) return 0;
-  if (runs_general(p, net)) {
-    if (int rc = general_refusal(p, net, td != 0, false)) return rc;
-    *family = DPI_FAMILY_GENERAL;
-    return 0;
-  }
-  if (gbm_too_wide(p, net)) return gbm_too_wide_refusal();
-  if (!spec_shape(p->e.kind, net->d.H, net->d.L))
+  const Route r = route(route_pair(p, net, td != 0, mlp_split(net)), ROUTE_FAMILY);
+  *family = r.family;
+  if (r.code) return refuse(r);
+  if (net->d.kind == 1 && !r.general && !spec_shape(p->e.kind, net->d.H, net->d.L))
     return fail(DPI_ERR_UNSUPPORTED, "pair_family: unsupported equation/network shape");
   return 0;
 }
@@ -1135,16 +1032,15 @@ static bool base_tag_ok(const void* ws, int n) {
 }
 
 int dpi_point_baseline(dpi_problem p, dpi_net net, const float* tx, int n, void* ws, size_t ws_bytes, void* stream) {
-  int rc = check_pair(p, net);
+  Route r;
+  int rc = route_call(p, net, ROUTE_BASELINE, &r);
   if (rc) return rc;
   if (n < 0 || (n && (!tx || !ws))) return fail(DPI_ERR_ARG, "point_baseline: bad arguments");
   if (n == 0) return 0;
   const WsLayout w = ws_layout(net, n, 0, 1 + p->e.nx);
   if (ws_bytes < w.partial) return fail(DPI_ERR_WORKSPACE, "workspace too small");
   if (net->d.kind == 2) return pis_baseline(p);
-  Launch q = baseline_launch(tx, n, ws, w, (hipStream_t)stream);
-  route_launch(q, p, net, ws, w);
-  if (!dispatch_any(p, net, q)) return fail(DPI_ERR_UNSUPPORTED, "point_baseline: unsupported equation/network shape");
+  if ((rc = launch_unit(p, net, baseline_launch(r, tx, n, ws, w, (hipStream_t)stream)))) return rc;
   HIPCHK(hipGetLastError());
   base_tag_set(ws, n);
   return 0;
@@ -1191,12 +1087,10 @@ static uint32_t next_ready_seq() {
   return s;
 }
 // Sets a.tail / a.tail_order / a.tail_seq of a k_paths or k_paths_fb launch.  Units run only where the
-// kernel instance has them (tail_shape, no TD), the call has a park and asks for both estimators.
-static void arm_tail(PathArgs& a, dpi_problem p, dpi_net net, const WsLayout& w) {
+// kernel instance has them (Route::tail), the call has a park and asks for both estimators.
+static void arm_tail(PathArgs& a, const Route& r, dpi_problem p, const WsLayout& w) {
   a.tail = 0;
-  if (!a.park || a.flags != DPI_BOTH || p->td_dt > 0.f || net->d.kind != 1 ||
-      !tail_shape(p->e.kind, net->d.H, net->d.L, net->d.act))
-    return;
+  if (!r.tail || !a.park || a.flags != DPI_BOTH) return;
   const int nblk = a.n * a.nbp, nb = (p->e.nx + 3) >> 2, ng = p->e.kind == DPI_EQ_CHA ? 1 : p->e.ncomp;
   const int cap = tail_cap(nblk, (long long)w.park_rows, nb, ng);
   const char* env = std::getenv("DPI_TAIL");
@@ -1211,22 +1105,22 @@ static void arm_tail(PathArgs& a, dpi_problem p, dpi_net net, const WsLayout& w)
 // k_paths_gen's ranges are in the block list.
 // What dpi_launch_units reports: the calling thread's last k_paths / k_paths_fb launch.
 static thread_local int g_units_tail = 0, g_units_grid = 0, g_units_launches = 0;
-static bool dispatch_units(const dpi_problem_s* p, const dpi_net_s* net, Launch q, const PathArgs& a, int nbase) {
+static int launch_units(const dpi_problem_s* p, const dpi_net_s* net, Launch q, const PathArgs& a, int nbase) {
   const int nblk = a.n * a.nbp;
   q.a = &a;
   q.nblocks = (int)tail_grid(nbase, nblk, a.tail);
   g_units_tail = a.tail;
   g_units_grid = q.nblocks;
   g_units_launches = a.tail && tail_two_launches() ? 2 : 1;
-  if (!a.tail || !tail_two_launches()) return dispatch_any(p, net, q);
+  if (!a.tail || !tail_two_launches()) return launch_unit(p, net, q);
   q.nblocks -= a.tail;
-  if (!dispatch_any(p, net, q)) return false;
+  if (int rc = launch_unit(p, net, q)) return rc;
   PathArgs a2 = a;
   a2.unit0 = tail_first(nbase, nblk, a.tail, 1);
   q.a = &a2;
   q.nblocks = a.tail;
   q.t0 = q.t1 = nullptr;
-  return dispatch_any(p, net, q);
+  return launch_unit(p, net, q);
 }
 
 int dpi_launch_units(int* tail, int* grid, int* launches) {
@@ -1239,19 +1133,17 @@ int dpi_launch_units(int* tail, int* grid, int* launches) {
 
 static size_t hess_extra(int n, int M, int nx, size_t* moff);
 // Validates a label-moments call and fills its PathArgs (shared by dpi_label_moments,
-// dpi_label_prepare and, with `hess`, the Hessian-label calls: GBM with MLP or zero nets only, their
-// own error texts, and the Hessian block sums and moments behind the layout, hess_extra).  Returns
-// 0, or the error; *w receives the workspace layout.
+// dpi_label_prepare and, with ROUTE_HESS, the Hessian-label calls: their own error texts, and the
+// Hessian block sums and moments behind the layout, hess_extra).  Returns 0, or the error; *w receives
+// the workspace layout, *r the call's route.
 static int label_args(dpi_problem p, dpi_net net, const float* tx, int n, int M, int K, uint64_t seed,
                       uint32_t epoch, uint32_t point_base, int m_begin, int m_end, int flags, bool need_moments,
-                      const float* moments, void* ws, size_t ws_bytes, WsLayout* w, PathArgs* pa, bool hess = false) {
+                      const float* moments, void* ws, size_t ws_bytes, WsLayout* w, PathArgs* pa, Route* r,
+                      RouteCall call = ROUTE_PATHS) {
   const bool prepared = !need_moments || (flags & DPI_PREPARED);  // dpi_label_prepare, or its prepared call
-  int rc = check_pair(p, net);
+  const bool hess = call == ROUTE_HESS;
+  int rc = route_call(p, net, call, r);
   if (rc) return rc;
-  if (hess && runs_general(p, net)) return general_refusal(p, net, false, true);
-  if (hess && p->e.kind != DPI_EQ_GBM)
-    return fail(DPI_ERR_UNSUPPORTED, "Hessian labels need a SimpleDiffusionEquationWithHessian (GBMEquationComplexExact)");
-  if (hess && net->d.kind == 2) return fail(DPI_ERR_UNSUPPORTED, "Hessian labels: MLP or ZeroSolution networks only");
   if (n < 0 || (n && (!tx || !ws || (need_moments && !moments))) || K < 1 || M < 1 || m_begin < 0 || m_end > M ||
       m_end <= m_begin || (m_begin % P) || ((m_end % P) && m_end != M) || !(flags & DPI_BOTH) ||
       (flags & ~(DPI_BOTH | DPI_PREPARED)) || epoch > 0xFFFFFFu)
@@ -1269,7 +1161,7 @@ static int label_args(dpi_problem p, dpi_net net, const float* tx, int n, int M,
                                  ": at most DPI_PATHS_PER_CALL_MAX paths per call");
   // the noise staging region only for dpi_label_prepare and the DPI_PREPARED call it feeds
   const bool noise = prepared && gbm_noise_prep(p, net);
-  *w = ws_layout(net, n, M, F, noise, park_pair(p, net));
+  *w = ws_layout(net, n, M, F, noise, r->park);
   if (hess) {
     size_t moff;
     if (ws_bytes < al256(w->total) + hess_extra(n, M, p->e.nx, &moff))
@@ -1303,10 +1195,11 @@ static int label_args(dpi_problem p, dpi_net net, const float* tx, int n, int M,
   a.order = path_order();
   a.split = mlp_split(net) ? 1 : 0;
   // the split specialised instances' park, when it holds a row for every path block of this call
-  if (a.split && !runs_general(p, net) && w->park_rows && (size_t)n * nbp <= w->park_rows)
+  if (r->parks && (size_t)n * nbp <= w->park_rows)
     a.park = (float*)(b + w->park);
   a.td_dt = p->td_dt;
-  return 0;
+  // the route's late refusal (dpi_label_prepare launches no unit: it leaves that to the label call)
+  return need_moments && r->code ? refuse(*r) : 0;
 }
 
 // Arms the fused reduce of a path launch: k_paths' last block per point counts on the workspace's
@@ -1328,8 +1221,9 @@ static int moments_impl(dpi_problem p, dpi_net net, const float* tx, int n, int 
                         void* ws, size_t ws_bytes, void* stream, float* y, float bound) {
   WsLayout w;
   PathArgs a;
+  Route r;
   int rc = label_args(p, net, tx, n, M, K, seed, epoch, point_base, m_begin, m_end, flags, true, moments, ws, ws_bytes,
-                      &w, &a);
+                      &w, &a, &r);
   if (rc || n == 0) return rc;
   const int F = 1 + p->e.nx, nbp = a.nbp;
   char* b = (char*)ws;
@@ -1338,12 +1232,7 @@ static int moments_impl(dpi_problem p, dpi_net net, const float* tx, int n, int 
   if (net->d.kind == 2) {
     if ((rc = pis_paths(p, net, tx, n, K, a, w, b, st, (flags & DPI_PREPARED) != 0))) return rc;
   } else {
-    Launch q = path_launch(a, n * nbp, st);
-    route_launch(q, p, net, ws, w);
-    q.td = p->td_dt > 0.f;
-    if (q.td && p->e.nx > NXP_MAX)
-      return fail(DPI_ERR_UNSUPPORTED, "label_moments: the TD estimators (ESTIMATE_DELTA_T > 0) are compiled for "
-                                       "nx <= 128 (NXP_MAX)");
+    Launch q = path_launch(r, a, n * nbp, ws, w, st);
     take_timer(q.t0, q.t1);
     if ((flags & DPI_PREPARED) && stages_prepare(p, net)) a.noise = (const float*)(b + w.noise);
     if (nbp <= 64 && fused_reduce_on()) {  // k_paths' last block per point reduces and finalizes
@@ -1352,9 +1241,8 @@ static int moments_impl(dpi_problem p, dpi_net net, const float* tx, int n, int 
                                  "was enqueued on this workspace (the fused reduce's tickets are zeroed there)");
       arm_fused_reduce(a, net, ws, w, M, flags, moments, y, bound);
     }
-    arm_tail(a, p, net, w);
-    if (!dispatch_units(p, net, q, a, 0))
-      return fail(DPI_ERR_UNSUPPORTED, "label_moments: unsupported equation/network shape");
+    arm_tail(a, r, p, w);
+    if ((rc = launch_units(p, net, q, a, 0))) return rc;
     if (a.tickets) {
       HIPCHK(hipGetLastError());
       return 0;
@@ -1370,45 +1258,37 @@ static int moments_impl(dpi_problem p, dpi_net net, const float* tx, int n, int 
 
 // The one-launch dpi_sample_with_gradients (DPI_FUSED_BASE=0: two launches; read per call).
 static bool fused_base_on() { return env_int("DPI_FUSED_BASE", 1) != 0; }
-// The nets and problems k_paths_fb is instantiated for (dpi_dispatch.h fused_base_shape, the one
-// predicate do_launch instantiates by): first-order Cha / OU labels of zero nets or ELU MLP nets
-// (H % 32 == 0, the fused-MLP instances; not OU 4 x 128).  The run-time conditions on top: no TD,
-// nx <= NXP_MAX, and MLP nets in the fp16-split mode; the rest runs the two-launch form.
-static bool fused_base_ok(dpi_problem p, dpi_net net) {
-  if (p->td_dt > 0.f || p->e.nx > NXP_MAX || runs_general(p, net)) return false;
-  if (net->d.kind == 0) return fused_base_shape(p->e.kind, 0, 0, true, DPI_ACT_ELU);
-  return net->d.kind == 1 && mlp_split(net) && fused_base_shape(p->e.kind, net->d.H, net->d.L, false, net->d.act);
-}
 // sample_with_gradients (picard/data.py:211-223) as one call.  First-order Cha / OU labels of MLP
 // and zero nets (no TD; <= 64 path blocks per point, so the label reduce runs in the path launch):
 // ONE k_paths launch of n base blocks (base_point: the point's draws 1-3, g(x), f_b, bx; published
 // per point) ahead of the n nbp path blocks, which draw their point themselves, roll out, and wait
 // for the point's record only before its first use — the baseline's latency-bound chain runs beside
 // the rollouts instead of ahead of them.  Otherwise the points' draws inside the baseline launch
-// (k_baseline with SampleSpec), then the rollout / label kernel.  PISGradNet:
-// dpi_sample_points_t + dpi_generate_with_gradients.
+// (k_baseline with SampleSpec), then the rollout / label kernel.  Which pairs may take the one-launch
+// form: Route::fused.  PISGradNet: dpi_sample_points_t + dpi_generate_with_gradients.
 int dpi_sample_with_gradients(dpi_problem p, dpi_net net, int n, int M, int K, uint64_t seed, uint32_t epoch,
                               uint32_t point_base, float eps, int t_factors, int flags, float sample_bound, float* tx,
                               float* y, float* moments, void* ws, size_t ws_bytes, void* stream) {
-  int rc = check_pair(p, net);
+  Route r;
+  int rc = route_call(p, net, ROUTE_FUSED, &r);
   if (rc) return rc;
   if (n < 0 || M < 1 || K < 1 || epoch > 0xFFFFFFu || t_factors < 0 || t_factors > 4096)
     return fail(DPI_ERR_ARG, "sample_with_gradients: bad arguments (n >= 0, M, K >= 1, t_factors in [0, 4096])");
   if (n == 0) return 0;
   if (!tx || !y || !moments) return fail(DPI_ERR_ARG, "sample_with_gradients: null tx, y or moments");
   const int F = 1 + p->e.nx;
-  const WsLayout w = ws_layout(net, n, M, F, false, park_pair(p, net));
+  const WsLayout w = ws_layout(net, n, M, F, false, r.park);
   if (!ws || ws_bytes < w.total) return fail(DPI_ERR_WORKSPACE, "workspace too small");
   if (net->d.kind == 2) {
     if ((rc = dpi_sample_points_t(p, n, seed, epoch, point_base, eps, t_factors, tx, stream))) return rc;
     return dpi_generate_with_gradients(p, net, tx, n, M, K, seed, epoch, point_base, flags, sample_bound, y, moments, ws,
                                        ws_bytes, stream);
   }
-  if (fused_base_ok(p, net) && (M + P - 1) / P <= 64 && fused_reduce_on() && fused_base_on()) {
+  if (r.fused && (M + P - 1) / P <= 64 && fused_reduce_on() && fused_base_on()) {
     WsLayout wl;
     PathArgs a;
     if ((rc = label_args(p, net, tx, n, M, K, seed, epoch, point_base, 0, M, flags, true, moments, ws, ws_bytes, &wl,
-                         &a)))
+                         &a, &r, ROUTE_FUSED)))
       return rc;
     char* b = (char*)ws;
     arm_fused_reduce(a, net, ws, wl, M, flags, moments, y, sample_bound);
@@ -1418,12 +1298,11 @@ int dpi_sample_with_gradients(dpi_problem p, dpi_net net, int n, int M, int K, u
     fb.ready = (unsigned long long*)(b + wl.ready);
     fb.ready_seq = next_ready_seq();
     fb.smp = sample_spec(p, seed, epoch, point_base, eps, t_factors, tx);
-    Launch q = path_launch(a, n + n * a.nbp, (hipStream_t)stream);
+    Launch q = path_launch(r, a, n + n * a.nbp, ws, wl, (hipStream_t)stream);
     q.fbase = &fb;
     take_timer(q.t0, q.t1);
-    arm_tail(a, p, net, wl);
-    if (!dispatch_units(p, net, q, a, n))
-      return fail(DPI_ERR_UNSUPPORTED, "sample_with_gradients: unsupported equation/network shape");
+    arm_tail(a, r, p, wl);
+    if ((rc = launch_units(p, net, q, a, n))) return rc;
     HIPCHK(hipGetLastError());
     base_tag_set(ws, n);  // the base blocks zeroed the tickets and left the baseline in ws
     return 0;
@@ -1438,7 +1317,8 @@ int dpi_sample_with_gradients(dpi_problem p, dpi_net net, int n, int M, int K, u
 // for MLP / zero networks: each baseline workgroup samples its own point first.
 int dpi_sample_points_baseline(dpi_problem p, dpi_net net, int n, uint64_t seed, uint32_t epoch, uint32_t point_base,
                                float eps, int t_factors, float* tx, void* ws, size_t ws_bytes, void* stream) {
-  int rc = check_pair(p, net);
+  Route r;
+  int rc = route_call(p, net, ROUTE_BASELINE, &r);
   if (rc) return rc;
   if (n < 0 || (n && (!tx || !ws)) || epoch > 0xFFFFFFu || t_factors < 0 || t_factors > 4096)
     return fail(DPI_ERR_ARG, "sample_points_baseline: bad arguments (t_factors in [0, 4096])");
@@ -1449,11 +1329,9 @@ int dpi_sample_points_baseline(dpi_problem p, dpi_net net, int n, uint64_t seed,
   }
   const WsLayout w = ws_layout(net, n, 0, 1 + p->e.nx);
   if (ws_bytes < w.partial) return fail(DPI_ERR_WORKSPACE, "workspace too small");
-  Launch q = baseline_launch(tx, n, ws, w, (hipStream_t)stream);
+  Launch q = baseline_launch(r, tx, n, ws, w, (hipStream_t)stream);
   q.smp = sample_spec(p, seed, epoch, point_base, eps, t_factors, tx);
-  route_launch(q, p, net, ws, w);
-  if (!dispatch_any(p, net, q))
-    return fail(DPI_ERR_UNSUPPORTED, "sample_points_baseline: unsupported equation/network shape");
+  if ((rc = launch_unit(p, net, q))) return rc;
   HIPCHK(hipGetLastError());
   base_tag_set(ws, n);
   return 0;
@@ -1511,8 +1389,9 @@ int dpi_label_prepare(dpi_problem p, dpi_net net, const float* tx, int n, int M,
                       uint32_t point_base, int m_begin, int m_end, int flags, void* ws, size_t ws_bytes, void* stream) {
   WsLayout w;
   PathArgs a;
+  Route r;
   int rc = label_args(p, net, tx, n, M, K, seed, epoch, point_base, m_begin, m_end, flags & DPI_BOTH, false, nullptr,
-                      ws, ws_bytes, &w, &a);
+                      ws, ws_bytes, &w, &a, &r);
   if (rc || n == 0) return rc;
   if (!stages_prepare(p, net)) return 0;  // nothing to stage: the fused path kernels do it all
   {
@@ -1615,12 +1494,13 @@ int dpi_label_finalize(dpi_problem p, const float* moments, int n, int M, int fl
 int dpi_generate_with_gradients(dpi_problem p, dpi_net net, const float* tx, int n, int M, int K, uint64_t seed,
                                 uint32_t epoch, uint32_t point_base, int flags, float sample_bound, float* y,
                                 float* moments, void* ws, size_t ws_bytes, void* stream) {
-  int rc = check_pair(p, net);
+  Route r;
+  int rc = route_call(p, net, ROUTE_BASELINE, &r);
   if (rc) return rc;
   if (n < 0 || M < 1 || K < 1) return fail(DPI_ERR_ARG, "generate_with_gradients: bad arguments (n >= 0, M, K >= 1)");
   if (n == 0) return 0;
   const int F = 1 + p->e.nx;
-  const WsLayout w = ws_layout(net, n, M, F, false, park_pair(p, net));
+  const WsLayout w = ws_layout(net, n, M, F, false, r.park);
   if (!ws || ws_bytes < w.total) return fail(DPI_ERR_WORKSPACE, "workspace too small");
   if (!moments) return fail(DPI_ERR_ARG, "generate_with_gradients: moments buffer (n*2*(1+nx) floats) required");
   if ((rc = dpi_point_baseline(p, net, tx, n, ws, ws_bytes, stream))) return rc;
@@ -1664,8 +1544,9 @@ static int hess_moments_impl(dpi_problem p, dpi_net net, const float* tx, int n,
   // Hessian instances are GBM and non-TD.
   WsLayout w;
   PathArgs a;
+  Route r;
   int rc = label_args(p, net, tx, n, M, K, seed, epoch, point_base, m_begin, m_end, flags, true, moments, ws, ws_bytes,
-                      &w, &a, true);
+                      &w, &a, &r, ROUTE_HESS);
   if (rc || n == 0) return rc;
   const int nx = p->e.nx, F = 1 + nx, C = nx * nx, nbp = a.nbp;
   char* b = (char*)ws;
@@ -1678,13 +1559,10 @@ static int hess_moments_impl(dpi_problem p, dpi_net net, const float* tx, int n,
   a.hpart = (float*)(b + al256(w.total));  // [packed block sums | moments] behind the layout (hess_extra)
   const int NT = (nx + 15) / 16;
   hipStream_t st = (hipStream_t)stream;
-  if (p->e.nx > NXP_MAX)
-    return fail(DPI_ERR_UNSUPPORTED, "Hessian labels: compiled for nx <= 128 (NXP_MAX)");
-  Launch q = path_launch(a, n * nbp, st);
+  Launch q = path_launch(r, a, n * nbp, ws, w, st);
   q.hess = true;
   take_timer(q.t0, q.t1);
-  if (!dispatch_any(p, net, q))
-    return fail(DPI_ERR_UNSUPPORTED, "Hessian labels: unsupported network shape (GBM: width <= 64)");
+  if ((rc = launch_unit(p, net, q))) return rc;
   HIPCHK(hipGetLastError());
   hipLaunchKernelGGL(k_reduce, dim3(n, (2 * F + 3) / 4), dim3(256), 0, st, a.partial, n, F, nbp, moments, a.gx,
                      1.0f / (float)M, (flags & DPI_TERMINAL) ? 1 : 0, bound, y, F + C, net_status(net));
@@ -1727,15 +1605,15 @@ int dpi_label_finalize_hessians(dpi_problem p, const float* moments, const float
 int dpi_generate_with_gradients_and_hessians(dpi_problem p, dpi_net net, const float* tx, int n, int M, int K,
                                              uint64_t seed, uint32_t epoch, uint32_t point_base, float sample_bound,
                                              float* y, void* ws, size_t ws_bytes, void* stream) {
-  int rc = check_pair(p, net);
-  if (rc) return rc;
-  if (net->head || net->term || (p->e.kind == DPI_EQ_GBM && runs_general(p, net)))
-    return general_refusal(p, net, false, true);  // no Hessian labels
+  if (!p || !net) return fail(DPI_ERR_ARG, "null problem or net");
+  // in this call's order: a general-family Cha / OU value net hears about the equation, after the arguments
+  const Route r = pair_route(p, net, ROUTE_HESS);
+  if (r.code && (r.stage == ROUTE_PAIR || (r.general && (r.head || r.term || p->e.kind == DPI_EQ_GBM)))) return refuse(r);
+  int rc;
   if (n < 0 || (!y && n) || M < 1 || M > 1024 * P)
     return fail(DPI_ERR_ARG, "generate_with_gradients_and_hessians: bad arguments (1 <= M <= 65536)");
   if (n == 0) return 0;
-  if (p->e.kind != DPI_EQ_GBM)
-    return fail(DPI_ERR_UNSUPPORTED, "Hessian labels need a SimpleDiffusionEquationWithHessian (GBMEquationComplexExact)");
+  if (p->e.kind != DPI_EQ_GBM) return fail(DPI_ERR_UNSUPPORTED, ROUTE_HESS_EQ);
   if ((rc = dpi_point_baseline(p, net, tx, n, ws, ws_bytes, stream))) return rc;
   const WsLayout w = ws_layout(net, n, M, 1 + p->e.nx);
   size_t moff;

@@ -54,7 +54,7 @@ def case_id(c):
 
 def _build():
     cases = []
-    # every row of the unit table (csrc/dpi_dispatch.h DPI_UNITS), as tests/test_gpu_dispatch_rows.py ROWS
+    # every row of the unit table (csrc/dpi_route.h DPI_UNITS), as tests/test_gpu_dispatch_rows.py ROWS
     rows = [(eq, act, var) for var in ("plain", "td", "wide") for act in ("ELU", "Tanh") for eq in ("cha", "ou", "gbm")]
     rows += [("cha", "ELU", "fb"), ("ou", "ELU", "fb")]
     for eq, act, var in rows:

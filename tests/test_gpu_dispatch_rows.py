@@ -1,4 +1,4 @@
-"""Every row of the path-kernel unit table (csrc/dpi_dispatch.h DPI_UNITS), one tiny labelling call
+"""Every row of the path-kernel unit table (csrc/dpi_route.h DPI_UNITS), one tiny labelling call
 per kernel instance the row can launch, against the fp64 oracle (oracle/dpi_oracle.py).
 
 Rows: {Cha, OU, GBM} x {ELU, Tanh} x {plain, TD, wide} and the two fused-baseline rows (Cha / OU

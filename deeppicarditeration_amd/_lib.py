@@ -27,6 +27,7 @@ DPI_STATUS_NONFINITE = 1
 DPI_STATUS_HANDOFF = 2
 DPI_STATUS_SLOTS = 64
 DPI_FAMILY_SPECIALISED, DPI_FAMILY_GENERAL = 0, 1  # dpi_pair_family
+DPI_FIT_LOSS_SQUARE, DPI_FIT_LOSS_CLIP = 0, 1  # dpi_fit_gradients
 
 c_int, c_double, c_float, c_size_t, c_void_p, c_uint32, c_uint64 = (
     ctypes.c_int, ctypes.c_double, ctypes.c_float, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64)
@@ -96,6 +97,10 @@ SIGNATURES = {
     "dpi_generate_with_gradients_and_hessians": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_uint64,
                                                          c_uint32, c_uint32, c_float, c_void_p, c_void_p, c_size_t,
                                                          c_void_p]),
+    "dpi_fit_workspace_bytes": (c_size_t, [c_int, c_int, P(c_int), c_int]),
+    "dpi_fit_gradients": (c_int, [c_int, c_int, P(c_int), c_int, P(c_void_p), P(c_void_p), P(c_void_p), P(c_void_p),
+                                  c_void_p, c_void_p, c_int, c_int, c_float, c_int, c_float, c_float, c_void_p,
+                                  c_void_p, c_size_t, c_void_p]),
 }
 
 _lib = None

@@ -20,15 +20,16 @@ ROOT = Path(__file__).resolve().parent
 REPO = ROOT.parent
 CSRC = ROOT / "csrc"
 def unit_files():
-    """dpi_kernels.hip, dpi_net.hip and one dpi_paths_<NAME>.hip per row X(NAME, ...) of DPI_UNITS
-    (csrc/dpi_route.h); a row without its file, or such a file without a row, is an error."""
+    """dpi_kernels.hip, dpi_net.hip, dpi_fit.hip (the fit's kernels: no row of the table) and one
+    dpi_paths_<NAME>.hip per row X(NAME, ...) of DPI_UNITS (csrc/dpi_route.h); a row without its file,
+    or such a file without a row, is an error."""
     import re
     rows = re.findall(r"^\s*X\((\w+),", (CSRC / "dpi_route.h").read_text(), flags=re.M)
     want = [f"dpi_paths_{r}.hip" for r in rows]
     odd = sorted(set(want) ^ {f.name for f in CSRC.glob("dpi_paths_*.hip")})
     if odd:
         raise RuntimeError(f"DPI_UNITS and csrc/dpi_paths_*.hip disagree on {', '.join(odd)}")
-    return ["dpi_kernels.hip", "dpi_net.hip", *want]
+    return ["dpi_kernels.hip", "dpi_net.hip", "dpi_fit.hip", *want]
 
 
 UNITS = unit_files()

@@ -1,8 +1,9 @@
 """YAML configuration surface of the reference (`picard/config.py`), without yacs (not in this
 image): the same default schema, `BASE:` chaining with `NAME` joining (config.py:229-257) and
 `KEY VALUE` command-line overrides (config.py:259-262), so the reference's experiment YAMLs load
-unchanged.  Keys added by this build (all under DATA): BACKEND ("hip"), SEED, EULER_STEPS,
-POINTS_PER_CALL.
+unchanged.  Keys added by this build: under DATA BACKEND ("hip"), SEED, EULER_STEPS,
+POINTS_PER_CALL; TRAIN.BACKEND ("torch": the fit's objectives in PyTorch-ROCm; "hip": loss and
+parameter gradients in the kernels of csrc/dpi_fit.h).
 """
 import ast
 import copy
@@ -117,7 +118,9 @@ def get_default_cfg() -> CfgNode:
     C.METHOD = _N({"cls": "Picard", "num_v_samples": 16, "K": 20, "dt": 0.005, "num_sub_iter": 100})
     C.PICARD = _N({"N": 1, "FORMULA": None})
     C.TRAIN = _N({"BATCH_SIZE": 2048, "N_EPOCHS": 1, "SUPERVISE_GRADIENT": None, "SUPERVISE_HESSIAN": None,
-                  "NUM_HESS_SAMPLES": -1})
+                  "NUM_HESS_SAMPLES": -1,
+                  # this build
+                  "BACKEND": "torch"})
     C.TRAIN.LOSS = _N({"beta": 0.0, "use_aux_loss": False, "weight_aux_loss": 0.1})
     C.TRAIN.LOSS.SCALER = _N({"cls": None})
     C.TRAIN.LOSS.SCALER.kwargs = _N(new_allowed=True)
@@ -184,5 +187,7 @@ def load_cfg(cfg_file: str, override: List[str] = None) -> CfgNode:
             cfg.DATA.MEMORY.RESERVED = cfg.DATA.RESERVED_MEMORY
         else:
             raise ValueError("Both RESERVED_MEMORY and MEMORY.RESERVED are set.")
+    if cfg.TRAIN.BACKEND not in ("torch", "hip"):
+        raise ValueError(f"TRAIN.BACKEND {cfg.TRAIN.BACKEND!r}: one of 'torch', 'hip'")
     cfg.freeze()
     return cfg

@@ -1,0 +1,130 @@
+// C ABI of the fit's device path (include/dpi.h: dpi_fit_workspace_bytes, dpi_fit_gradients); the
+// kernels are in dpi_fit.h.  Not a row of the unit table: nothing here depends on a (problem, network)
+// route.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdint>
+#include <string>
+
+#include "dpi_fit.h"
+#include "dpi_host.h"
+
+namespace {
+
+using namespace dpi;
+
+// shape checks shared by both entry points: 0, or the code with the text set
+int fit_shape(int n_in, int n_hidden, const int* widths, int B) {
+  if (n_in < 2 || n_hidden < 1 || !widths || B < 0)
+    return fail(DPI_ERR_ARG, "fit: bad shape (n_in = 1 + nx >= 2, n_hidden >= 1, widths, B >= 0)");
+  if (n_in > FIT_NIN_MAX)
+    return fail(DPI_ERR_UNSUPPORTED, "fit: nx = " + std::to_string(n_in - 1) + " > 256, the state dimensions the "
+                                     "fit kernels are compiled for");
+  if (n_hidden > FIT_LMAX)
+    return fail(DPI_ERR_UNSUPPORTED, "fit: " + std::to_string(n_hidden) + " hidden layers > 8");
+  for (int l = 0; l < n_hidden; ++l) {
+    if (widths[l] < 1) return fail(DPI_ERR_ARG, "fit: hidden width < 1");
+    if (widths[l] > FIT_WMAX)
+      return fail(DPI_ERR_UNSUPPORTED, "fit: hidden width " + std::to_string(widths[l]) + " > 256");
+  }
+  if (B > (1 << 24)) return fail(DPI_ERR_UNSUPPORTED, "fit: B > 2^24 rows in one batch");
+  return 0;
+}
+
+// the workspace layout: fills the offsets of `a` (n, L, tiles set) and returns the float count
+size_t fit_layout(FitArgs& a) {
+  const size_t R = (size_t)a.tiles * FIT_ROWS;
+  const int L = a.L;
+  size_t o = 0;
+  for (int l = 0; l <= L + 1; ++l) a.offA[l] = a.offP[l] = a.offD[l] = a.offZ[l] = a.offLB[l] = 0;
+  for (int l = 1; l <= L; ++l) { a.offA[l] = o; o += (size_t)a.n[l] * R; }
+  for (int l = 1; l <= L; ++l) { a.offP[l] = o; o += (size_t)a.n[l] * R; }
+  for (int l = 1; l <= L + 1; ++l) { a.offD[l] = o; o += (size_t)a.n[l] * R; }
+  for (int l = 1; l <= L + 1; ++l) { a.offZ[l] = o; o += (size_t)a.n[l] * R; }
+  for (int l = 0; l <= L; ++l) { a.offLB[l] = o; o += (size_t)a.n[l] * R; }
+  o += o & 1;  // the loss partials are doubles
+  a.offPart = o;
+  o += 2 * (size_t)a.tiles * (a.n[0] + 1);
+  return o;
+}
+
+void fit_dims(FitArgs& a, int n_in, int n_hidden, const int* widths, int B) {
+  a.L = n_hidden;
+  a.n[0] = n_in;
+  for (int l = 0; l < n_hidden; ++l) a.n[l + 1] = widths[l];
+  a.n[n_hidden + 1] = 1;
+  a.B = B;
+  a.tiles = (B + FIT_ROWS - 1) / FIT_ROWS;
+}
+
+}  // namespace
+
+extern "C" size_t dpi_fit_workspace_bytes(int n_in, int n_hidden, const int* widths, int B) {
+  if (fit_shape(n_in, n_hidden, widths, B)) return 0;
+  FitArgs a{};
+  fit_dims(a, n_in, n_hidden, widths, B);
+  return fit_layout(a) * sizeof(float);
+}
+
+extern "C" int dpi_fit_gradients(int n_in, int n_hidden, const int* widths, int act, const float* const* W,
+                                 const float* const* b, float* const* dW, float* const* db, const float* tx,
+                                 const float* y, int y_stride, int B, float beta, int loss_kind, float clip,
+                                 float c, float* losses, void* ws, size_t ws_bytes, void* stream) {
+  int rc = fit_shape(n_in, n_hidden, widths, B);
+  if (rc) return rc;
+  if (act != DPI_ACT_ELU && act != DPI_ACT_TANH)
+    return fail(DPI_ERR_UNSUPPORTED, "fit_gradients: activation " + std::to_string(act) + " (DPI_ACT_ELU or "
+                                     "DPI_ACT_TANH for every hidden layer)");
+  if (loss_kind != DPI_FIT_LOSS_SQUARE && loss_kind != DPI_FIT_LOSS_CLIP)
+    return fail(DPI_ERR_ARG, "fit_gradients: loss kind (DPI_FIT_LOSS_SQUARE or DPI_FIT_LOSS_CLIP)");
+  if (loss_kind == DPI_FIT_LOSS_CLIP && !(clip > 0.f && std::isfinite(clip)))
+    return fail(DPI_ERR_ARG, "fit_gradients: clip must be positive and finite");
+  if (!std::isfinite(beta) || !(c >= 0.f) || !std::isfinite(c))
+    return fail(DPI_ERR_ARG, "fit_gradients: beta must be finite and the gradient weight c >= 0 and finite");
+  if (y_stride < n_in) return fail(DPI_ERR_ARG, "fit_gradients: y row stride < 1 + nx");
+  if (B == 0) return 0;
+  if (!W || !b || !dW || !db) return fail(DPI_ERR_ARG, "fit_gradients: null pointer table (W, b, dW, db)");
+  for (int l = 0; l <= n_hidden; ++l)
+    if (!W[l] || !b[l] || !dW[l] || !db[l])
+      return fail(DPI_ERR_ARG, "fit_gradients: null entry in a pointer table at layer " + std::to_string(l));
+  if (!tx || !y || !losses) return fail(DPI_ERR_ARG, "fit_gradients: null tx, y or losses");
+  FitArgs a{};
+  fit_dims(a, n_in, n_hidden, widths, B);
+  const size_t need = fit_layout(a) * sizeof(float);
+  if ((uintptr_t)ws % 8) return fail(DPI_ERR_ARG, "fit_gradients: the workspace must be 8-byte aligned");
+  if (!ws || ws_bytes < need)
+    return fail(DPI_ERR_WORKSPACE, "fit_gradients: workspace too small (" + std::to_string(ws_bytes) + " < " +
+                                   std::to_string(need) + " bytes, dpi_fit_workspace_bytes)");
+  for (int l = 0; l <= n_hidden; ++l) {
+    a.W[l] = W[l];
+    a.b[l] = b[l];
+    a.dW[l] = dW[l];
+    a.db[l] = db[l];
+  }
+  a.tx = tx;
+  a.y = y;
+  a.ystride = y_stride;
+  a.grad = c > 1e-9f ? 1 : 0;  // build_objective's threshold for the plain value fit
+  a.clipped = loss_kind == DPI_FIT_LOSS_CLIP;
+  a.beta = beta;
+  a.clip = clip;
+  a.c = c;
+  a.ws = (float*)ws;
+  a.losses = losses;
+  int blk = 0;
+  for (int l = 1; l <= n_hidden + 1; ++l) {
+    a.blk0[l - 1] = blk;
+    blk += ((a.n[l] + FIT_WT - 1) / FIT_WT) * ((a.n[l - 1] + FIT_WT - 1) / FIT_WT);
+  }
+  a.blk0[n_hidden + 1] = blk;
+  hipStream_t st = (hipStream_t)stream;
+  if (act == DPI_ACT_TANH)
+    hipLaunchKernelGGL(k_fit_rows<DPI_ACT_TANH>, dim3(a.tiles), dim3(FIT_NTH), 0, st, a);
+  else
+    hipLaunchKernelGGL(k_fit_rows<DPI_ACT_ELU>, dim3(a.tiles), dim3(FIT_NTH), 0, st, a);
+  HIPCHK(hipGetLastError());
+  hipLaunchKernelGGL(k_fit_wgrad, dim3(blk + 1), dim3(256), 0, st, a);
+  HIPCHK(hipGetLastError());
+  return 0;
+}

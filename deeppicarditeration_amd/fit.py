@@ -1,5 +1,7 @@
 """The outer fit's objectives — what the reference's solution wrappers compute per training batch
-(SURVEY.md §8f rank 3).  PyTorch-ROCm, not HIP: the fit consumes the device-resident labels.
+(SURVEY.md §8f rank 3).  PyTorch-ROCm by default (TRAIN.BACKEND: torch); under TRAIN.BACKEND: hip the
+loss and the parameter gradients of the value and gradient kinds come from the HIP kernels of
+csrc/dpi_fit.h (`device_objective`).  The fit consumes the device-resident labels.
 
 - `value_objective`: PicardBaseSolution.training_step (picard/solution.py:74-81), the exp(beta t)
   weighted value loss;
@@ -14,6 +16,7 @@
   (solution_jac.py:219-259), plus the Hessian losses (all nx^2 entries, or NUM_HESS_SAMPLES of them
   drawn with `random.sample` as there);
 - the loss scalers of solution_jac.py:13-109 and LossFnLinearClip (solution.py:22-33);
+- `device_objective`: `value_objective` and `gradient_objective` (FixedLossScaler) on the device;
 - `build_objective`: the wrapper choice of PicardRunner.get_solution (picard_iteration.py:113-118)
   and PicardSolutionGradientWrapper.construct_solution / __init__ (solution_jac.py:112-136).
 
@@ -209,6 +212,133 @@ def gradient_hessian_objective(beta, loss_fn, scaler, nx, num_hess_samples=-1):
     return objective
 
 
+BACKENDS = ("torch", "hip")  # TRAIN.BACKEND
+
+
+class _DevicePlan:
+    """What `device_objective` needs of one network, checked once: the Linear layers of a
+    construct_mlp value network (all-ELU or all-Tanh hidden layers, one output, no NETWORK.BOUND), its
+    parameters in state-dict order and the C-ABI shape arguments.  Everything else is refused by name;
+    there is no fallback to the torch objectives."""
+
+    def __init__(self, net, nx):
+        from . import _lib
+        self.net = net
+        kind = type(net).__name__
+        if kind in ("PicardSolutionEnforceTerminal", "PISGradNet"):
+            raise NotImplementedError(f"TRAIN.BACKEND: hip with {kind}: the fit kernels take construct_mlp value "
+                                      "networks only")
+        if not isinstance(net, torch.nn.Sequential):
+            raise NotImplementedError(f"TRAIN.BACKEND: hip with a {kind} network: the fit kernels take construct_mlp "
+                                      "value networks only")
+        mods = list(net)
+        if mods and isinstance(mods[-1], torch.nn.Hardtanh):
+            raise NotImplementedError("TRAIN.BACKEND: hip with NETWORK.BOUND: the fit kernels have no output clamp")
+        lin, acts = mods[0::2], mods[1::2]
+        if len(mods) < 3 or len(mods) % 2 == 0 or not all(isinstance(m, torch.nn.Linear) for m in lin):
+            raise NotImplementedError("TRAIN.BACKEND: hip: the network is not a construct_mlp Linear / activation chain")
+        codes = {torch.nn.ELU: _lib.DPI_ACT_ELU, torch.nn.Tanh: _lib.DPI_ACT_TANH}
+        kinds = {type(m) for m in acts}
+        if len(kinds) != 1 or next(iter(kinds)) not in codes:
+            raise NotImplementedError("TRAIN.BACKEND: hip with NETWORK.ACTIVATIONS "
+                                      f"{[type(m).__name__ for m in acts]}: all ELU or all Tanh")
+        if any(isinstance(m, torch.nn.ELU) and m.alpha != 1.0 for m in acts):
+            raise NotImplementedError("TRAIN.BACKEND: hip with ELU alpha != 1")
+        if lin[-1].out_features != 1:
+            raise NotImplementedError(f"TRAIN.BACKEND: hip with a network of {lin[-1].out_features} outputs (a gradient "
+                                      "head): value networks only")
+        if any(m.bias is None for m in lin):
+            raise NotImplementedError("TRAIN.BACKEND: hip with a Linear layer without bias")
+        if lin[0].in_features != 1 + nx:
+            raise ValueError(f"network input width {lin[0].in_features} != 1 + nx = {1 + nx}")
+        self.weights = [m.weight for m in lin]
+        self.biases = [m.bias for m in lin]
+        for p in self.weights + self.biases:
+            if p.dtype != torch.float32 or not p.is_contiguous():
+                raise NotImplementedError(f"TRAIN.BACKEND: hip with {p.dtype} / non-contiguous parameters: fp32 "
+                                          "contiguous parameters only (DATA.FLOAT: float)")
+        widths = [m.out_features for m in lin[:-1]]
+        if len(widths) > 8 or max(widths) > 256 or nx > 256:
+            raise NotImplementedError(f"TRAIN.BACKEND: hip with NETWORK.NEURONS {widths}, nx = {nx}: 1-8 hidden layers "
+                                      "of width <= 256 and nx <= 256")
+        self.act = codes[next(iter(kinds))]
+        self.n_in, self.n_hidden = 1 + nx, len(widths)
+        self.widths = (_lib.c_int * len(widths))(*widths)
+        self.params = [p for m in lin for p in (m.weight, m.bias)]  # state-dict order
+        self.ws = None
+
+    def table(self, tensors):
+        from . import _lib
+        return (_lib.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+
+
+class _DeviceFit(torch.autograd.Function):
+    """losses (2 + nx,) = (total, v_loss, g_loss[nx]) of one batch from dpi_fit_gradients, launched on
+    torch's current stream; the parameter gradients it computed are kept and handed to the parameters
+    in backward, scaled by the gradient arriving at losses[0]."""
+
+    @staticmethod
+    def forward(ctx, plan, tx, y, beta, loss_kind, clip, c, *params):
+        from . import _lib
+        lib = _lib.load()
+        if tx.device.type != "cuda":
+            raise _lib.DPIError("TRAIN.BACKEND: hip needs the batch on the GPU (there is no CPU fallback)")
+        if tx.dtype != torch.float32 or y.dtype != torch.float32:
+            raise NotImplementedError(f"TRAIN.BACKEND: hip with {tx.dtype} batches: fp32 only (DATA.FLOAT: float)")
+        tx, y = tx.detach().contiguous(), y.detach()
+        if y.stride(-1) != 1:
+            y = y.contiguous()
+        B, nx = int(tx.shape[0]), plan.n_in - 1
+        need = int(lib.dpi_fit_workspace_bytes(plan.n_in, plan.n_hidden, plan.widths, B))
+        if plan.ws is None or plan.ws.numel() < need or plan.ws.device != tx.device:
+            plan.ws = torch.empty(max(need, 1), dtype=torch.uint8, device=tx.device)
+        grads = [torch.empty_like(p) for p in params]
+        losses = torch.empty(2 + nx, dtype=torch.float32, device=tx.device)
+        _lib.check(lib.dpi_fit_gradients(plan.n_in, plan.n_hidden, plan.widths, plan.act, plan.table(params[0::2]),
+                                         plan.table(params[1::2]), plan.table(grads[0::2]), plan.table(grads[1::2]),
+                                         tx.data_ptr(), y.data_ptr(), int(y.stride(0)), B, float(beta), loss_kind,
+                                         float(clip), float(c), losses.data_ptr(), plan.ws.data_ptr(), plan.ws.numel(),
+                                         torch.cuda.current_stream(tx.device).cuda_stream), "dpi_fit_gradients")
+        ctx.grads = grads
+        total, parts = losses[:1], losses[1:]
+        ctx.mark_non_differentiable(parts)
+        return total, parts
+
+    @staticmethod
+    def backward(ctx, g_total, _g_parts):
+        return (None,) * 7 + tuple(torch._foreach_mul(ctx.grads, g_total.reshape(())))
+
+
+def device_objective(beta, loss_fn, scaler, nx):
+    """The device form of `value_objective` (scaler None, or a FixedLossScaler of weight <= 1e-9) and of
+    `gradient_objective` with a FixedLossScaler: loss and parameter gradients from the HIP kernels of
+    csrc/dpi_fit.h, same signature and `info` keys.  The optimizer stays torch's:
+    `loss.sum().backward()` delivers the gradients the forward launch computed."""
+    from . import _lib
+    if scaler is not None and not isinstance(scaler, FixedLossScaler):
+        raise NotImplementedError(f"TRAIN.BACKEND: hip with {type(scaler).__name__}: FixedLossScaler only")
+    if isinstance(loss_fn, LossFnLinearClip):
+        loss_kind, clip = _lib.DPI_FIT_LOSS_CLIP, float(loss_fn.clip)
+    elif loss_fn is torch.square:
+        loss_kind, clip = _lib.DPI_FIT_LOSS_SQUARE, 0.0
+    else:
+        raise NotImplementedError(f"TRAIN.BACKEND: hip with the loss function {loss_fn!r}: the square or LossFnLinearClip")
+    c = 0.0 if scaler is None else float(scaler.fixed_weight)
+    value_only = c <= 1e-9
+    plans = {}
+
+    def objective(net, tx, y):
+        plan = plans.get(id(net))
+        if plan is None or plan.net is not net:
+            plan = plans[id(net)] = _DevicePlan(net, nx)
+        total, parts = _DeviceFit.apply(plan, tx, y, beta, loss_kind, clip, 0.0 if value_only else c, *plan.params)
+        if value_only:
+            return total, {}
+        return total, {"train_gradient_loss(unscaled)": parts[1:].sum(dim=-1, keepdim=True),
+                       "train_value_loss": parts[:1]}
+    return objective
+
+
 def make_scaler(scaler_cfg):
     """solution_jac.py:132-136: no SCALER.cls means FixedLossScaler(1.0)."""
     if scaler_cfg is None or scaler_cfg.get("cls") is None:
@@ -216,12 +346,18 @@ def make_scaler(scaler_cfg):
     return LossScaler.get_class(scaler_cfg["cls"])(**dict(scaler_cfg.get("kwargs") or {}))
 
 
-def build_objective(train_cfg, nx, supervise_gradient, supervise_hessian, output_dim=1):
+def build_objective(train_cfg, nx, supervise_gradient, supervise_hessian, output_dim=1, backend="torch"):
     """PicardRunner.get_solution (picard_iteration.py:113-118) + the wrappers' construct_solution
     (solution_jac.py:112-119): returns (objective, kind) with kind in {"value", "gradient",
     "gradient_hessian", "head_value_gradient", "head_only_gradient"}.  output_dim: the network's
     output width (1: a Value net; 1 + nx / nx: a ValueGradient / OnlyGradient head).  A
-    FixedLossScaler of weight <= 1e-9 falls back to the plain value fit (Value nets)."""
+    FixedLossScaler of weight <= 1e-9 falls back to the plain value fit (Value nets).
+    backend (TRAIN.BACKEND): "torch" builds the objectives above; "hip" builds `device_objective` for the
+    kinds "value" and "gradient" with FixedLossScaler and refuses every other option by name."""
+    if backend not in BACKENDS:
+        raise ValueError(f"TRAIN.BACKEND {backend!r}: one of {BACKENDS}")
+    if backend == "hip":
+        return _build_device_objective(train_cfg, nx, supervise_gradient, supervise_hessian, output_dim)
     loss_cfg = train_cfg["LOSS"]
     beta = float(loss_cfg["beta"])
     loss_fn = make_loss_fn(loss_cfg.get("FN"))
@@ -257,6 +393,30 @@ def build_objective(train_cfg, nx, supervise_gradient, supervise_hessian, output
             raise NotImplementedError(f"{scaler} has no scale_g_h: SUPERVISE_HESSIAN needs FixedHessianLossScaler")
         return gradient_hessian_objective(beta, loss_fn, scaler, nx, n_h), "gradient_hessian"
     return gradient_objective(beta, loss_fn, scaler, nx), "gradient"
+
+
+def _build_device_objective(train_cfg, nx, supervise_gradient, supervise_hessian, output_dim):
+    """build_objective under TRAIN.BACKEND: hip.  The options the fit kernels do not cover raise
+    NotImplementedError naming the option; the network itself is checked at the first batch."""
+    loss_cfg = train_cfg["LOSS"]
+    beta = float(loss_cfg["beta"])
+    loss_fn = make_loss_fn(loss_cfg.get("FN"))
+    if output_dim != 1:
+        raise NotImplementedError("TRAIN.BACKEND: hip with NETWORK.TYPE ValueGradient / OnlyGradient (a gradient head "
+                                  f"of {output_dim} outputs): value networks only")
+    if supervise_hessian:
+        raise NotImplementedError("TRAIN.BACKEND: hip with TRAIN.SUPERVISE_HESSIAN: the fit kernels have the value "
+                                  "and gradient losses only")
+    if not supervise_gradient:
+        return device_objective(beta, loss_fn, None, nx), "value"
+    if bool(loss_cfg.get("use_aux_loss")):
+        raise NotImplementedError("TRAIN.LOSS.use_aux_loss applies to ValueGradient networks only")
+    scaler = make_scaler(loss_cfg.get("SCALER"))
+    if not isinstance(scaler, FixedLossScaler):
+        raise NotImplementedError(f"TRAIN.BACKEND: hip with TRAIN.LOSS.SCALER {type(scaler).__name__}: "
+                                  "FixedLossScaler only")
+    kind = "value" if scaler.fixed_weight <= 1e-9 else "gradient"
+    return device_objective(beta, loss_fn, scaler, nx), kind
 
 
 def make_optimizer(params, opt_cfg):

@@ -229,7 +229,8 @@ class PicardRunner:
         replay the in-memory cache, shuffled when DATA.SHUFFLE is set (dataset.py:203-255)."""
         t = self.cfg.TRAIN
         objective, self.fit_kind = build_objective(t, self.equation.nx, self.supervise_gradient,
-                                                   self.supervise_hessian, self.output_dim)
+                                                   self.supervise_hessian, self.output_dim,
+                                                   backend=str(t.get("BACKEND", "torch")))
         opt, sched = make_optimizer(net.parameters(), t.OPTIMIZER)
         n = tx.shape[0]
         bs = int(t.BATCH_SIZE) if t.BATCH_SIZE else n
@@ -346,7 +347,8 @@ class PicardRunner:
         n = int(tx.shape[0])
         rec = {"iter": self.i, "labels": n, "label_s": t_labels, "labels_per_s": n / t_labels,
                "path_labels_per_s": None if self.cfg.DATA.EXACT else n * M / t_labels, "ranks": self.world,
-               "fit_s": t_fit, "fit": self.fit_kind, "loss": loss, "rel_l2_u": metrics.get("rRMSE"), **metrics}
+               "fit_s": t_fit, "fit": self.fit_kind, "fit_backend": str(self.cfg.TRAIN.get("BACKEND", "torch")),
+               "loss": loss, "rel_l2_u": metrics.get("rRMSE"), **metrics}
         self.history.append(rec)
         with open(self.exp_dir / "history.jsonl", "a") as f:
             f.write(json.dumps(rec) + "\n")

@@ -407,6 +407,33 @@ int dpi_generate_with_gradients_and_hessians(dpi_problem p, dpi_net net, const f
                                              float sample_bound, float* y, void* ws, size_t ws_bytes,
                                              void* stream);
 
+/* --- the outer fit's loss and parameter gradients (additions within ABI 8: no existing entry point
+ * changes).  Replaces, per training batch, PicardBaseSolution.training_step (picard/solution.py:74-81)
+ * and PicardSolutionGradientWrapper.training_step with FixedLossScaler (picard/solution_jac.py:167-213,
+ * :71-82) together with the double backward torch runs for them, for construct_mlp value networks:
+ *   loss = v_loss + c sum_d g_loss[d],  v_loss = mean_B w rho(u - y[:, 0]),
+ *   g_loss[d] = mean_B w rho(d_d u - y[:, 1 + d]),  w = exp(beta t),
+ * rho the square (DPI_FIT_LOSS_SQUARE) or LossFnLinearClip(clip) (DPI_FIT_LOSS_CLIP).  c <= 1e-9 is the
+ * plain value fit: the gradient losses are not formed (losses[2:] = 0).
+ * Net: n_in = 1 + nx <= 257, 1..8 hidden layers each 1..256 wide (more: DPI_ERR_UNSUPPORTED), act
+ * DPI_ACT_ELU or DPI_ACT_TANH for every hidden layer, one output.  W, b, dW, db: host tables of
+ * n_hidden + 1 device pointers, layer by layer: torch's Linear.weight (out, in) row-major and bias, read
+ * in place, and the gradients of the same shapes, which are overwritten (never accumulated into).
+ * tx (B, n_in) and y (B rows of y_stride >= n_in floats: value label, gradient labels, anything after
+ * them is not read) fp32 on the device.  losses: 2 + nx floats on the device (total, v_loss, g_loss[nx]).
+ * Exact fp32; every sum over the batch runs in a fixed order, so gradients and losses are bitwise
+ * reproducible.  Two launches on `stream`, nothing is read back to the host.  Arguments are checked
+ * before any device work; B = 0 is an empty batch: scalar checks only, nothing launched.
+ * ws: 8-byte aligned, >= dpi_fit_workspace_bytes(n_in, n_hidden, widths, B) bytes (0 for a shape the call
+ * would refuse), else DPI_ERR_WORKSPACE. */
+#define DPI_FIT_LOSS_SQUARE 0
+#define DPI_FIT_LOSS_CLIP 1
+size_t dpi_fit_workspace_bytes(int n_in, int n_hidden, const int* widths, int B);
+int dpi_fit_gradients(int n_in, int n_hidden, const int* widths, int act, const float* const* W,
+                      const float* const* b, float* const* dW, float* const* db, const float* tx, const float* y,
+                      int y_stride, int B, float beta, int loss_kind, float clip, float c, float* losses, void* ws,
+                      size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,77 @@
+"""Time one optimizer step of the fit — objective, backward and Adam step — under both fit backends
+(DESIGN.md §5.1): the device objective (TRAIN.BACKEND: hip, csrc/dpi_fit.h) and the torch objective it
+bypasses, in one process on one device, alternating, PAIRS runs each.
+
+Two shapes: the shipped Burgers fit (B = 512, nx = 100, 4 x 128 ELU, c = 1) and the shape of the r03c
+`picard train` log (B = 128, nx = 8, [32, 32] ELU, c = 0.1).  Per run: warm-up steps, then REPS steps each
+bracketed by its own pair of HIP events; the median is reported (ms/step) with the minimum beside it.  One
+JSON line per run, then one per shape with the acceptance figures of the project's protocol (§2.1): every
+device run below every torch run, and the gain against 3 x the spread of the torch runs.
+
+    python tools/time_fit.py [--reps 30] [--warmup 5] [--pairs 3]
+"""
+import argparse
+import json
+import sys
+from pathlib import Path
+
+import torch
+
+sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
+import deeppicarditeration_amd as dpi  # noqa: E402
+from deeppicarditeration_amd import fit  # noqa: E402
+
+SHAPES = [("burgers B512 nx100 4x128 ELU c1", 512, 100, [128] * 4, 1.0),
+          ("r03c B128 nx8 2x32 ELU c0.1", 128, 8, [32, 32], 0.1)]
+
+
+def time_steps(backend, B, nx, widths, c, reps, warmup):
+    torch.manual_seed(0)
+    net = dpi.construct_mlp(1 + nx, 1, widths, ["ELU"] * len(widths), None).to("cuda")
+    scaler = fit.FixedLossScaler(c)
+    objective = (fit.device_objective if backend == "hip" else fit.gradient_objective)(0.0, torch.square, scaler, nx)
+    opt = torch.optim.Adam(net.parameters(), lr=1e-3)
+    tx = torch.cat([torch.rand(B, 1), torch.randn(B, nx)], 1).to("cuda")
+    y = (torch.randn(B, 1 + nx) * 0.5).to("cuda")
+    batch = [(tx, y)]
+    for _ in range(warmup):
+        fit.train_steps(net, objective, opt, batch)
+    torch.cuda.synchronize()
+    evs = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        losses = fit.train_steps(net, objective, opt, batch)
+        b.record()
+        evs.append((a, b))
+    torch.cuda.synchronize()
+    assert torch.isfinite(losses).all()
+    t = sorted(a.elapsed_time(b) for a, b in evs)
+    return {"ms_median": t[len(t) // 2], "ms_min": t[0]}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=30)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--pairs", type=int, default=3)
+    a = ap.parse_args()
+    assert a.reps >= 20, "the median of at least 20 steps"
+    for name, B, nx, widths, c in SHAPES:
+        runs = {"hip": [], "torch": []}
+        for _ in range(a.pairs):
+            for backend in ("hip", "torch"):
+                r = time_steps(backend, B, nx, widths, c, a.reps, a.warmup)
+                runs[backend].append(r["ms_median"])
+                print(json.dumps({"shape": name, "backend": backend, **r}), flush=True)
+        spread = max(runs["torch"]) - min(runs["torch"])
+        gain = min(runs["torch"]) - max(runs["hip"])
+        print(json.dumps({"shape": name, "hip_ms": runs["hip"], "torch_ms": runs["torch"],
+                          "every_hip_run_faster": max(runs["hip"]) < min(runs["torch"]), "gain_ms": gain,
+                          "torch_spread_ms": spread, "gain_over_3_spreads": gain > 3 * spread,
+                          "ratio_torch_over_hip": [min(runs["torch"]) / max(runs["hip"]),
+                                                   max(runs["torch"]) / min(runs["hip"])]}), flush=True)
+
+
+if __name__ == "__main__":
+    main()

@@ -17,6 +17,9 @@
 //
 // Rows of the last tile past B are dead: they load zeros, run like live rows, and their loss terms and
 // seeds are selected to +0; k_fit_wgrad never reads them.
+//
+// For a PISGradNet only nn_module runs here, as a differentiable primitive between torch's time networks
+// and torch's loss: k_fit_core_fwd, k_fit_core_bwd and k_fit_core_wgrad at the end of this file.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -412,6 +415,287 @@ __global__ __launch_bounds__(256) void k_fit_wgrad(const FitArgs a) {
     }
     __syncthreads();
     // the chunk's sum: the two products and the even / odd rows apart, added pairwise
+    float c0 = 0.f, c1 = 0.f, g0 = 0.f, g1 = 0.f;
+    double bc0 = 0.0, bc1 = 0.0;
+    int r = 0;
+    for (; r + 2 <= nr; r += 2) {
+      c0 = fmaf(sZ[tj][r], sA[ti][r], c0);
+      c1 = fmaf(sZ[tj][r + 1], sA[ti][r + 1], c1);
+      if (a.grad) {
+        g0 = fmaf(sD[tj][r], sLB[ti][r], g0);
+        g1 = fmaf(sD[tj][r + 1], sLB[ti][r + 1], g1);
+      }
+      if (bias) {
+        bc0 += (double)sZ[tj][r];
+        bc1 += (double)sZ[tj][r + 1];
+      }
+    }
+    if (r < nr) {
+      c0 = fmaf(sZ[tj][r], sA[ti][r], c0);
+      if (a.grad) g0 = fmaf(sD[tj][r], sLB[ti][r], g0);
+      if (bias) bc0 += (double)sZ[tj][r];
+    }
+    tot += (double)((c0 + c1) + (g0 + g1));
+    btot += bc0 + bc1;
+  }
+  const int j = j0 + tj, i = i0 + ti;
+  if (j < nout && i < nin) a.dW[l - 1][(size_t)j * nin + i] = (float)tot;
+  if (bias && j < nout) a.db[l - 1][j] = (float)btot;
+}
+
+// ---- PISGradNet's nn_module as a differentiable primitive ("The PISGradNet core") ----
+//
+// Rows a_0 = (tau (64), x (nx)); N = nn_module(a_0) (nx outputs), sp = x . N, q = d sp / d x = N +
+// (J^T x)[x columns].  The loss around (sp, q) is torch's; its cotangents e = d loss / d sp and
+// r = d loss / d q come back to the second entry.  ELU only.
+//
+//   k_fit_core_fwd    passes 1 (forward) and 2 (adjoint with delta_{L+1} = x): writes sp, q and parks the state
+//   k_fit_core_bwd    passes 3 (tangent from lambdabar_0 = (0, r)) and 4 (reverse from zbar_{L+1} = e x + r, down
+//                     to abar_0, whose tau columns are the gradient of tau)
+//   k_fit_core_wgrad  k_fit_wgrad's row walk for every layer, the nx-wide output layer included
+//
+// Same tile as k_fit_rows (64 rows, lane = row, fit_mv / fit_mvT), but widths run to 512, so there is one LDS
+// vector, not two: a layer's result is parked first ([unit][row], as k_fit_rows parks it anyway) and, after
+// a barrier, staged from the workgroup's own parked columns for the next layer.  a_0 is parked as well: its x
+// columns are delta_{L+1} of the output layer's tangent term.
+constexpr int CORE_LMAX = 4;     // hidden layers
+constexpr int CORE_WMAX = 512;   // hidden width: CORE_WMAX x FIT_ROWS floats are the 128 KB LDS vector
+constexpr int CORE_NT = 64;      // tau columns (PISGradNet.channels)
+constexpr int CORE_NX_MAX = 128;
+
+struct FitCoreArgs {
+  const float* W[CORE_LMAX + 1];  // layer l = 1 .. L + 1 at [l - 1]: (n[l], n[l - 1]) row-major
+  const float* b[CORE_LMAX + 1];
+  float* dW[CORE_LMAX + 1];
+  float* db[CORE_LMAX + 1];
+  int n[CORE_LMAX + 2];  // n[0] = 64 + nx, n[1 .. L] hidden widths, n[L + 1] = nx
+  int L;
+  int B, tiles;
+  int grad;              // forward: form q (pass 2); backward: r is given (pass 3)
+  const float* tau;      // (B, taustride >= 64)
+  const float* x;        // (B, xstride >= nx)
+  int taustride, xstride;
+  float* sp;             // (B)
+  float* q;              // (B, nx)
+  const float* e;        // (B)
+  const float* r;        // (B, nx)
+  float* dtau;           // (B, 64)
+  float* ws;
+  size_t offA[CORE_LMAX + 2];   // a_l, l = 0 .. L
+  size_t offP[CORE_LMAX + 2];   // act'(z_l), l = 1 .. L
+  size_t offD[CORE_LMAX + 2];   // delta_l, l = 1 .. L; [L + 1] is the x columns of a_0
+  size_t offZ[CORE_LMAX + 2];   // lambda_l, then zeta_l, then zbar_l, l = 1 .. L; zbar_{L+1}
+  size_t offLB[CORE_LMAX + 2];  // lambdabar_l, l = 0 .. L
+  size_t offN;                  // N, nx units
+  int blk0[CORE_LMAX + 2];      // k_fit_core_wgrad: first workgroup of layer l at [l - 1]; [L + 1] = their count
+};
+
+// the LDS vector <- the tile's columns of a parked [unit][row] array of n units
+__device__ __forceinline__ void core_stage(float* buf, const float* __restrict__ src, int n, size_t R, int tile,
+                                           int tid) {
+  for (int k = tid; k < n * FIT_ROWS; k += FIT_NTH)
+    buf[k] = src[(size_t)(k >> 6) * R + (size_t)tile * FIT_ROWS + (k & 63)];
+}
+
+__global__ __launch_bounds__(FIT_NTH) void k_fit_core_fwd(const FitCoreArgs a) {
+  __shared__ float buf[CORE_WMAX * FIT_ROWS];
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int tile = blockIdx.x;
+  const int row = tile * FIT_ROWS + lane;
+  const bool live = row < a.B;
+  const size_t R = (size_t)a.tiles * FIT_ROWS;
+  const int L = a.L;
+  const int n0 = a.n[0], nx = a.n[L + 1];
+  float* ws = a.ws;
+
+  // a_0 = (tau, x), parked and staged; dead rows are zeros
+  {
+    float* A0 = ws + a.offA[0];
+    for (int k = tid; k < FIT_ROWS * n0; k += FIT_NTH) {
+      const int r = k / n0, i = k - r * n0;
+      const int gr = tile * FIT_ROWS + r;
+      float v = 0.f;
+      if (gr < a.B)
+        v = i < CORE_NT ? a.tau[(size_t)gr * a.taustride + i] : a.x[(size_t)gr * a.xstride + (i - CORE_NT)];
+      buf[i * FIT_ROWS + r] = v;
+      A0[(size_t)i * R + gr] = v;
+    }
+  }
+  __syncthreads();
+
+  // 1. forward
+  for (int l = 1; l <= L; ++l) {
+    const float* bl = a.b[l - 1];
+    float* A = ws + a.offA[l];
+    float* P = ws + a.offP[l];
+    fit_mv(a.W[l - 1], a.n[l], a.n[l - 1], buf, wv, lane, [&](int j, float z) {
+      float v, d;
+      fit_act<DPI_ACT_ELU>(z + bl[j], v, d);
+      A[(size_t)j * R + row] = v;
+      P[(size_t)j * R + row] = d;
+    });
+    __syncthreads();
+    core_stage(buf, A, a.n[l], R, tile, tid);
+    __syncthreads();
+  }
+  // N = W_{L+1} a_L + b_{L+1}
+  float* N = ws + a.offN;
+  {
+    const float* bo = a.b[L];
+    fit_mv(a.W[L], nx, a.n[L], buf, wv, lane, [&](int j, float z) { N[(size_t)j * R + row] = z + bo[j]; });
+  }
+  __syncthreads();
+  // delta_{L+1} = x; sp = x . N, units in order as 4 partial sums
+  core_stage(buf, ws + a.offD[L + 1], nx, R, tile, tid);
+  __syncthreads();
+  if (wv == 0) {
+    float s[FIT_PS] = {0.f, 0.f, 0.f, 0.f};
+    for (int j = 0; j < nx; ++j)
+      s[j & (FIT_PS - 1)] = fmaf(buf[j * FIT_ROWS + lane], N[(size_t)j * R + row], s[j & (FIT_PS - 1)]);
+    if (live) a.sp[row] = (s[0] + s[1]) + (s[2] + s[3]);
+  }
+  if (!a.grad) return;
+
+  // 2. adjoint, downward: lambda_L = W_{L+1}^T x, delta_l = lambda_l act'(z_l), lambda_{l-1} = W_l^T delta_l
+  for (int l = L + 1; l >= 2; --l) {
+    float* P = ws + a.offP[l - 1];
+    float* Z = ws + a.offZ[l - 1];
+    float* D = ws + a.offD[l - 1];
+    fit_mvT(a.W[l - 1], a.n[l], a.n[l - 1], buf, wv, lane, [&](int i, float lam) {
+      const size_t o = (size_t)i * R + row;
+      Z[o] = lam;
+      D[o] = lam * P[o];
+    });
+    __syncthreads();
+    core_stage(buf, D, a.n[l - 1], R, tile, tid);
+    __syncthreads();
+  }
+  // lambda_0: its x columns complete q = N + (J^T x)
+  fit_mvT(a.W[0], a.n[1], n0, buf, wv, lane, [&](int i, float lam) {
+    if (i >= CORE_NT && live) a.q[(size_t)row * nx + (i - CORE_NT)] = N[(size_t)(i - CORE_NT) * R + row] + lam;
+  });
+}
+
+__global__ __launch_bounds__(FIT_NTH) void k_fit_core_bwd(const FitCoreArgs a) {
+  __shared__ float buf[CORE_WMAX * FIT_ROWS];
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int tile = blockIdx.x;
+  const int row = tile * FIT_ROWS + lane;
+  const bool live = row < a.B;
+  const size_t R = (size_t)a.tiles * FIT_ROWS;
+  const int L = a.L;
+  const int n0 = a.n[0], nx = a.n[L + 1];
+  float* ws = a.ws;
+
+  if (a.grad) {
+    // 3. tangent of the adjoint chain, upward, from lambdabar_0 = (0_tau, r)
+    {
+      float* LB0 = ws + a.offLB[0];
+      for (int k = tid; k < FIT_ROWS * n0; k += FIT_NTH) {
+        const int r = k / n0, i = k - r * n0;
+        const int gr = tile * FIT_ROWS + r;
+        const float v = (gr < a.B && i >= CORE_NT) ? a.r[(size_t)gr * nx + (i - CORE_NT)] : 0.f;
+        buf[i * FIT_ROWS + r] = v;
+        LB0[(size_t)i * R + gr] = v;
+      }
+    }
+    __syncthreads();
+    for (int l = 1; l <= L; ++l) {
+      float* A = ws + a.offA[l];
+      float* P = ws + a.offP[l];
+      float* Z = ws + a.offZ[l];
+      float* LB = ws + a.offLB[l];
+      fit_mv(a.W[l - 1], a.n[l], a.n[l - 1], buf, wv, lane, [&](int j, float db) {
+        const size_t o = (size_t)j * R + row;
+        const float d = P[o];
+        LB[o] = db * d;
+        Z[o] = db * Z[o] * fit_act_d2<DPI_ACT_ELU>(A[o], d);
+      });
+      __syncthreads();
+      if (l < L) {
+        core_stage(buf, LB, a.n[l], R, tile, tid);
+        __syncthreads();
+      }
+    }
+  }
+
+  // 4. reverse, downward: zbar_{L+1} = e x + r, zbar_l = abar_l act'(z_l) + zeta_l, abar_{l-1} = W_l^T zbar_l
+  {
+    float* ZO = ws + a.offZ[L + 1];
+    const float* X = ws + a.offD[L + 1];
+    for (int k = tid; k < FIT_ROWS * nx; k += FIT_NTH) {
+      const int r = k / nx, i = k - r * nx;
+      const int gr = tile * FIT_ROWS + r;
+      float v = 0.f;
+      if (gr < a.B) {
+        v = a.e[gr] * X[(size_t)i * R + gr];
+        if (a.grad) v += a.r[(size_t)gr * nx + i];
+      }
+      buf[i * FIT_ROWS + r] = v;
+      ZO[(size_t)i * R + gr] = v;
+    }
+  }
+  __syncthreads();
+  for (int l = L + 1; l >= 2; --l) {
+    float* P = ws + a.offP[l - 1];
+    float* Z = ws + a.offZ[l - 1];
+    fit_mvT(a.W[l - 1], a.n[l], a.n[l - 1], buf, wv, lane, [&](int i, float ab) {
+      const size_t o = (size_t)i * R + row;
+      float zb = ab * P[o];
+      if (a.grad) zb += Z[o];
+      Z[o] = zb;
+    });
+    __syncthreads();
+    core_stage(buf, Z, a.n[l - 1], R, tile, tid);
+    __syncthreads();
+  }
+  // abar_0: its tau columns
+  fit_mvT(a.W[0], a.n[1], n0, buf, wv, lane, [&](int i, float ab) {
+    if (i < CORE_NT && live) a.dtau[(size_t)row * CORE_NT + i] = ab;
+  });
+}
+
+// dW_l = sum_rows delta_l lambdabar_{l-1}^T + zbar_l a_{l-1}^T, db_l = sum_rows zbar_l for l = 1 .. L + 1, rows in
+// order (k_fit_wgrad's walk; here a_0 is parked and the output layer has nx units and a bias like the others)
+__global__ __launch_bounds__(256) void k_fit_core_wgrad(const FitCoreArgs a) {
+  __shared__ float sD[FIT_WT][FIT_CS], sZ[FIT_WT][FIT_CS], sLB[FIT_WT][FIT_CS], sA[FIT_WT][FIT_CS];
+  const int tid = threadIdx.x;
+  const size_t R = (size_t)a.tiles * FIT_ROWS;
+  const int blk = blockIdx.x;
+  int l = 1;
+  while (blk >= a.blk0[l]) ++l;  // blk0[l - 1] <= blk < blk0[l]
+  const int nout = a.n[l], nin = a.n[l - 1];
+  const int nit = (nin + FIT_WT - 1) / FIT_WT;
+  const int rel = blk - a.blk0[l - 1];
+  const int j0 = rel / nit * FIT_WT, i0 = (rel - rel / nit * nit) * FIT_WT;
+  const float* D = a.ws + a.offD[l];
+  const float* Z = a.ws + a.offZ[l];
+  const float* LB = a.ws + a.offLB[l - 1];
+  const float* A = a.ws + a.offA[l - 1];
+  const int tj = tid >> 4, ti = tid & 15;
+  const bool bias = i0 == 0 && ti == 0;
+  double tot = 0.0, btot = 0.0;
+  for (int r0 = 0; r0 < a.B; r0 += FIT_ROWS) {
+    const int nr = min(FIT_ROWS, a.B - r0);
+    __syncthreads();
+    for (int k = tid; k < FIT_WT * FIT_ROWS; k += 256) {
+      const int u = k >> 6, r = k & 63;
+      if (r < nr) {
+        const int j = min(j0 + u, nout - 1), i = min(i0 + u, nin - 1);
+        const size_t row = (size_t)r0 + r;
+        sZ[u][r] = Z[(size_t)j * R + row];
+        sA[u][r] = A[(size_t)i * R + row];
+        if (a.grad) {
+          sD[u][r] = D[(size_t)j * R + row];
+          sLB[u][r] = LB[(size_t)i * R + row];
+        }
+      }
+    }
+    __syncthreads();
     float c0 = 0.f, c1 = 0.f, g0 = 0.f, g1 = 0.f;
     double bc0 = 0.0, bc1 = 0.0;
     int r = 0;

@@ -1,6 +1,7 @@
-// C ABI of the fit's device path (include/dpi.h: dpi_fit_workspace_bytes, dpi_fit_gradients); the
-// kernels are in dpi_fit.h.  Not a row of the unit table: nothing here depends on a (problem, network)
-// route.
+// C ABI of the fit's device path (include/dpi.h: dpi_fit_workspace_bytes, dpi_fit_gradients for
+// construct_mlp value networks; dpi_fit_core_workspace_bytes, dpi_fit_core_forward, dpi_fit_core_backward
+// for PISGradNet's nn_module); the kernels are in dpi_fit.h.  Not a row of the unit table: nothing here
+// depends on a (problem, network) route.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -58,7 +59,140 @@ void fit_dims(FitArgs& a, int n_in, int n_hidden, const int* widths, int B) {
   a.tiles = (B + FIT_ROWS - 1) / FIT_ROWS;
 }
 
+// ---- the PISGradNet core (dpi_fit_core_*)
+
+int core_shape(int nx, int n_hidden, const int* widths, int B) {
+  if (nx < 1 || n_hidden < 1 || !widths || B < 0)
+    return fail(DPI_ERR_ARG, "fit_core: bad shape (nx >= 1, n_hidden >= 1, widths, B >= 0)");
+  if (nx > CORE_NX_MAX)
+    return fail(DPI_ERR_UNSUPPORTED, "fit_core: nx = " + std::to_string(nx) + " > 128, PISGradNet's state dimensions");
+  if (n_hidden > CORE_LMAX)
+    return fail(DPI_ERR_UNSUPPORTED, "fit_core: " + std::to_string(n_hidden) + " hidden layers > 4");
+  for (int l = 0; l < n_hidden; ++l) {
+    if (widths[l] < 1) return fail(DPI_ERR_ARG, "fit_core: hidden width < 1");
+    if (widths[l] > CORE_WMAX)
+      return fail(DPI_ERR_UNSUPPORTED, "fit_core: hidden width " + std::to_string(widths[l]) + " > 512");
+  }
+  if (B > (1 << 24)) return fail(DPI_ERR_UNSUPPORTED, "fit_core: B > 2^24 rows in one batch");
+  return 0;
+}
+
+void core_dims(FitCoreArgs& a, int nx, int n_hidden, const int* widths, int B) {
+  a.L = n_hidden;
+  a.n[0] = CORE_NT + nx;
+  for (int l = 0; l < n_hidden; ++l) a.n[l + 1] = widths[l];
+  a.n[n_hidden + 1] = nx;
+  a.B = B;
+  a.tiles = (B + FIT_ROWS - 1) / FIT_ROWS;
+}
+
+// the workspace layout of the core: fills the offsets and returns the float count
+size_t core_layout(FitCoreArgs& a) {
+  const size_t R = (size_t)a.tiles * FIT_ROWS;
+  const int L = a.L;
+  size_t o = 0;
+  for (int l = 0; l <= L + 1; ++l) a.offA[l] = a.offP[l] = a.offD[l] = a.offZ[l] = a.offLB[l] = 0;
+  for (int l = 0; l <= L; ++l) { a.offA[l] = o; o += (size_t)a.n[l] * R; }
+  for (int l = 1; l <= L; ++l) { a.offP[l] = o; o += (size_t)a.n[l] * R; }
+  for (int l = 1; l <= L; ++l) { a.offD[l] = o; o += (size_t)a.n[l] * R; }
+  a.offD[L + 1] = a.offA[0] + (size_t)CORE_NT * R;  // delta_{L+1} = x, the last nx units of a_0
+  for (int l = 1; l <= L + 1; ++l) { a.offZ[l] = o; o += (size_t)a.n[l] * R; }
+  for (int l = 0; l <= L; ++l) { a.offLB[l] = o; o += (size_t)a.n[l] * R; }
+  a.offN = o;
+  o += (size_t)a.n[L + 1] * R;
+  return o;
+}
+
+// what both core entries check and fill: the shape, the parameter tables and the workspace
+int core_begin(FitCoreArgs& a, const char* who, int nx, int n_hidden, const int* widths, int B,
+               const float* const* W, const float* const* b, void* ws, size_t ws_bytes) {
+  const std::string w(who);
+  if (!W || !b) return fail(DPI_ERR_ARG, w + ": null pointer table (W, b)");
+  for (int l = 0; l <= n_hidden; ++l)
+    if (!W[l] || !b[l]) return fail(DPI_ERR_ARG, w + ": null entry in a pointer table at layer " + std::to_string(l));
+  core_dims(a, nx, n_hidden, widths, B);
+  const size_t need = core_layout(a) * sizeof(float);
+  if ((uintptr_t)ws % 4) return fail(DPI_ERR_ARG, w + ": the workspace must be 4-byte aligned");
+  if (!ws || ws_bytes < need)
+    return fail(DPI_ERR_WORKSPACE, w + ": workspace too small (" + std::to_string(ws_bytes) + " < " +
+                                   std::to_string(need) + " bytes, dpi_fit_core_workspace_bytes)");
+  for (int l = 0; l <= n_hidden; ++l) {
+    a.W[l] = W[l];
+    a.b[l] = b[l];
+  }
+  a.ws = (float*)ws;
+  return 0;
+}
+
 }  // namespace
+
+extern "C" size_t dpi_fit_core_workspace_bytes(int nx, int n_hidden, const int* widths, int B) {
+  if (core_shape(nx, n_hidden, widths, B)) return 0;
+  FitCoreArgs a{};
+  core_dims(a, nx, n_hidden, widths, B);
+  return core_layout(a) * sizeof(float);
+}
+
+extern "C" int dpi_fit_core_forward(int nx, int n_hidden, const int* widths, const float* const* W,
+                                    const float* const* b, const float* tau, int tau_stride, const float* x,
+                                    int x_stride, int B, float* sp, float* q, void* ws, size_t ws_bytes,
+                                    void* stream) {
+  int rc = core_shape(nx, n_hidden, widths, B);
+  if (rc) return rc;
+  if (tau_stride < CORE_NT || x_stride < nx)
+    return fail(DPI_ERR_ARG, "fit_core_forward: row stride of tau < 64 or of x < nx");
+  if (B == 0) return 0;
+  if (!tau || !x || !sp) return fail(DPI_ERR_ARG, "fit_core_forward: null tau, x or sp");
+  FitCoreArgs a{};
+  rc = core_begin(a, "fit_core_forward", nx, n_hidden, widths, B, W, b, ws, ws_bytes);
+  if (rc) return rc;
+  a.tau = tau;
+  a.x = x;
+  a.taustride = tau_stride;
+  a.xstride = x_stride;
+  a.sp = sp;
+  a.q = q;
+  a.grad = q ? 1 : 0;
+  hipLaunchKernelGGL(k_fit_core_fwd, dim3(a.tiles), dim3(FIT_NTH), 0, (hipStream_t)stream, a);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+extern "C" int dpi_fit_core_backward(int nx, int n_hidden, const int* widths, const float* const* W,
+                                     const float* const* b, float* const* dW, float* const* db, const float* e,
+                                     const float* r, int B, float* dtau, void* ws, size_t ws_bytes, void* stream) {
+  int rc = core_shape(nx, n_hidden, widths, B);
+  if (rc) return rc;
+  if (B == 0) return 0;
+  if (!dW || !db) return fail(DPI_ERR_ARG, "fit_core_backward: null pointer table (dW, db)");
+  for (int l = 0; l <= n_hidden; ++l)
+    if (!dW[l] || !db[l])
+      return fail(DPI_ERR_ARG, "fit_core_backward: null entry in a gradient table at layer " + std::to_string(l));
+  if (!e || !dtau) return fail(DPI_ERR_ARG, "fit_core_backward: null e or dtau");
+  FitCoreArgs a{};
+  rc = core_begin(a, "fit_core_backward", nx, n_hidden, widths, B, W, b, ws, ws_bytes);
+  if (rc) return rc;
+  for (int l = 0; l <= n_hidden; ++l) {
+    a.dW[l] = dW[l];
+    a.db[l] = db[l];
+  }
+  a.e = e;
+  a.r = r;
+  a.grad = r ? 1 : 0;
+  a.dtau = dtau;
+  int blk = 0;
+  for (int l = 1; l <= n_hidden + 1; ++l) {
+    a.blk0[l - 1] = blk;
+    blk += ((a.n[l] + FIT_WT - 1) / FIT_WT) * ((a.n[l - 1] + FIT_WT - 1) / FIT_WT);
+  }
+  a.blk0[n_hidden + 1] = blk;
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(k_fit_core_bwd, dim3(a.tiles), dim3(FIT_NTH), 0, st, a);
+  HIPCHK(hipGetLastError());
+  hipLaunchKernelGGL(k_fit_core_wgrad, dim3(blk), dim3(256), 0, st, a);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
 
 extern "C" size_t dpi_fit_workspace_bytes(int n_in, int n_hidden, const int* widths, int B) {
   if (fit_shape(n_in, n_hidden, widths, B)) return 0;

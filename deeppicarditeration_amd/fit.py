@@ -1,7 +1,9 @@
 """The outer fit's objectives — what the reference's solution wrappers compute per training batch
 (SURVEY.md §8f rank 3).  PyTorch-ROCm by default (TRAIN.BACKEND: torch); under TRAIN.BACKEND: hip the
 loss and the parameter gradients of the value and gradient kinds come from the HIP kernels of
-csrc/dpi_fit.h (`device_objective`).  The fit consumes the device-resident labels.
+csrc/dpi_fit.h (`device_objective`): in two launches for a construct_mlp value network;
+for a PISGradNet, nn_module and its double backward in three launches (`_PISCore`) between the time networks
+and the loss, which stay torch's.  The fit consumes the device-resident labels.
 
 - `value_objective`: PicardBaseSolution.training_step (picard/solution.py:74-81), the exp(beta t)
   weighted value loss;
@@ -16,7 +18,8 @@ csrc/dpi_fit.h (`device_objective`).  The fit consumes the devi
   (solution_jac.py:219-259), plus the Hessian losses (all nx^2 entries, or NUM_HESS_SAMPLES of them
   drawn with `random.sample` as there);
 - the loss scalers of solution_jac.py:13-109 and LossFnLinearClip (solution.py:22-33);
-- `device_objective`: `value_objective` and `gradient_objective` (FixedLossScaler) on the device;
+- `device_objective`: `value_objective` and `gradient_objective` (FixedLossScaler) on the device, for
+  construct_mlp value networks and for PISGradNet;
 - `build_objective`: the wrapper choice of PicardRunner.get_solution (picard_iteration.py:113-118)
   and PicardSolutionGradientWrapper.construct_solution / __init__ (solution_jac.py:112-136).
 
@@ -225,7 +228,7 @@ class _DevicePlan:
         from . import _lib
         self.net = net
         kind = type(net).__name__
-        if kind in ("PicardSolutionEnforceTerminal", "PISGradNet"):
+        if kind in ("PicardSolutionEnforceTerminal", "PISGradNet"):  # a PISGradNet takes _PISPlan
             raise NotImplementedError(f"TRAIN.BACKEND: hip with {kind}: the fit kernels take construct_mlp value "
                                       "networks only")
         if not isinstance(net, torch.nn.Sequential):
@@ -309,11 +312,153 @@ class _DeviceFit(torch.autograd.Function):
         return (None,) * 7 + tuple(torch._foreach_mul(ctx.grads, g_total.reshape(())))
 
 
+PIS_CHANNELS, PIS_LAYERS_MAX, PIS_WIDTH_MAX, PIS_NX_MAX = 64, 4, 512, 128  # csrc/dpi_fit.h CORE_*
+
+
+class _PISPlan:
+    """What `device_objective` needs of one PISGradNet (this build's class or the reference's of that
+    name), checked once and before the library is touched: the closed-form g and g_x behind g0, the
+    Linear layers of `nn_module` (the part the HIP core computes), its parameters in state-dict order
+    and the C-ABI shape arguments.  What the core does not cover is refused by name."""
+
+    def __init__(self, net, nx):
+        from . import _lib
+        self.net = net
+        owner = getattr(net.g0, "__self__", None)
+        if owner is None or type(owner).__name__ != "OUProcessEquation":
+            raise NotImplementedError("TRAIN.BACKEND: hip with a PISGradNet whose g0 is not the bound method g of an "
+                                      "OUProcessEquation: the device fit needs the closed-form gradient g_x of g0")
+        self.equation = owner
+        if net.channels != PIS_CHANNELS:
+            raise NotImplementedError(f"TRAIN.BACKEND: hip with PISGradNet channels = {net.channels}: the core kernels "
+                                      f"take {PIS_CHANNELS} time channels")
+        if net.dim != nx:
+            raise ValueError(f"PISGradNet dim {net.dim} != nx = {nx}")
+        mods = list(net.nn_module)
+        lin, acts = mods[0::2], mods[1::2]
+        if (len(mods) < 3 or len(mods) % 2 == 0 or not all(isinstance(m, torch.nn.Linear) and m.bias is not None
+                                                           for m in lin)
+                or not all(isinstance(m, torch.nn.ELU) and m.alpha == 1.0 for m in acts)):
+            raise NotImplementedError("TRAIN.BACKEND: hip with a PISGradNet whose nn_module is not a Linear / ELU "
+                                      "(alpha = 1) chain with biases")
+        widths = [m.out_features for m in lin[:-1]]
+        if len(widths) > PIS_LAYERS_MAX or max(widths) > PIS_WIDTH_MAX:
+            raise NotImplementedError(f"TRAIN.BACKEND: hip with PISGradNet NETWORK.NEURONS {widths}: 1-"
+                                      f"{PIS_LAYERS_MAX} hidden layers of width <= {PIS_WIDTH_MAX}")
+        if nx > PIS_NX_MAX:
+            raise NotImplementedError(f"TRAIN.BACKEND: hip with PISGradNet at nx = {nx}: nx <= {PIS_NX_MAX}")
+        if lin[0].in_features != PIS_CHANNELS + nx or lin[-1].out_features != nx:
+            raise ValueError(f"PISGradNet nn_module maps {lin[0].in_features} -> {lin[-1].out_features}, not "
+                             f"{PIS_CHANNELS} + nx -> nx")
+        for p in net.parameters():
+            if p.dtype != torch.float32 or not p.is_contiguous():
+                raise NotImplementedError(f"TRAIN.BACKEND: hip with PISGradNet and {p.dtype} / non-contiguous "
+                                          "parameters: fp32 contiguous parameters only (DATA.FLOAT: float)")
+        self.nx, self.n_hidden = nx, len(widths)
+        self.widths = (_lib.c_int * len(widths))(*widths)
+        self.params = [p for m in lin for p in (m.weight, m.bias)]  # state-dict order
+        self.ws = None
+        self.calls = 0  # forward calls so far: a backward must find the state of its own forward in ws
+
+    def table(self, tensors):
+        from . import _lib
+        return (_lib.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+
+
+class _PISCore(torch.autograd.Function):
+    """PISGradNet's nn_module N as one differentiable primitive: (tau (B, 64), x (B, nx),
+    *params) -> sp = x . N(tau, x) (B, 1) and q = d sp / d x (B, nx), from dpi_fit_core_forward; backward
+    is dpi_fit_core_backward (the gradients of tau and of the parameters; x is data and gets none), so
+    no torch double backward is involved.  grad False: only sp is formed, q is empty."""
+
+    @staticmethod
+    def forward(ctx, plan, grad, tau, x, *params):
+        from . import _lib
+        lib = _lib.load()
+        tau, x = tau.detach(), x.detach()
+        if tau.stride(-1) != 1:
+            tau = tau.contiguous()
+        if x.stride(-1) != 1:
+            x = x.contiguous()
+        B, nx = int(x.shape[0]), plan.nx
+        need = int(lib.dpi_fit_core_workspace_bytes(nx, plan.n_hidden, plan.widths, B))
+        if plan.ws is None or plan.ws.numel() < need or plan.ws.device != x.device:
+            plan.ws = torch.empty(max(need, 4), dtype=torch.uint8, device=x.device)
+        sp = torch.empty(B, 1, dtype=torch.float32, device=x.device)
+        q = torch.empty(B if grad else 0, nx, dtype=torch.float32, device=x.device)
+        _lib.check(lib.dpi_fit_core_forward(nx, plan.n_hidden, plan.widths, plan.table(params[0::2]),
+                                            plan.table(params[1::2]), tau.data_ptr(), int(tau.stride(0)), x.data_ptr(),
+                                            int(x.stride(0)), B, sp.data_ptr(), q.data_ptr() if grad else None,
+                                            plan.ws.data_ptr(), plan.ws.numel(),
+                                            torch.cuda.current_stream(x.device).cuda_stream), "dpi_fit_core_forward")
+        plan.calls += 1
+        ctx.plan, ctx.grad, ctx.call, ctx.params, ctx.B = plan, grad, plan.calls, params, B
+        if not grad:
+            ctx.mark_non_differentiable(q)
+        return sp, q
+
+    @staticmethod
+    def backward(ctx, g_sp, g_q):
+        from . import _lib
+        lib = _lib.load()
+        plan, params, B = ctx.plan, ctx.params, ctx.B
+        if plan.calls != ctx.call:
+            raise RuntimeError("the PISGradNet core's state was overwritten by a later forward call on the same "
+                               "network before this backward ran")
+        dev = plan.ws.device
+        e = (torch.zeros(B, 1, dtype=torch.float32, device=dev) if g_sp is None else g_sp.float().contiguous())
+        r = g_q.float().contiguous() if ctx.grad and g_q is not None else None
+        grads = [torch.empty_like(p) for p in params]
+        dtau = torch.empty(B, PIS_CHANNELS, dtype=torch.float32, device=dev)
+        _lib.check(lib.dpi_fit_core_backward(plan.nx, plan.n_hidden, plan.widths, plan.table(params[0::2]),
+                                             plan.table(params[1::2]), plan.table(grads[0::2]),
+                                             plan.table(grads[1::2]), e.data_ptr(), None if r is None else r.data_ptr(),
+                                             B, dtau.data_ptr(), plan.ws.data_ptr(), plan.ws.numel(),
+                                             torch.cuda.current_stream(dev).cuda_stream), "dpi_fit_core_backward")
+        return (None, None, dtau, None) + tuple(grads)
+
+
+def _pis_objective(plan, tx, y, beta, loss_fn, scaler, value_only):
+    """`value_objective` / `gradient_objective` on a PISGradNet u = s sp + (1 - s) g0(c x): the time
+    networks (t_encoder, smooth_net, the embedding) run in torch with ordinary autograd, the parameter-free
+    g0 part under no_grad from the equation's closed forms, sp and q = d sp / d x come from `_PISCore`, and
+    the loss is formed in torch ops."""
+    from . import _lib
+    if tx.dtype != torch.float32 or y.dtype != torch.float32:
+        raise NotImplementedError(f"TRAIN.BACKEND: hip with PISGradNet and {tx.dtype} batches: fp32 only "
+                                  "(DATA.FLOAT: float)")
+    if tx.device.type != "cuda":
+        raise _lib.DPIError("TRAIN.BACKEND: hip needs the batch on the GPU (there is no CPU fallback)")
+    net, nx = plan.net, plan.nx
+    tx = tx.detach()
+    t, x = torch.narrow(tx, -1, 0, 1), torch.narrow(tx, -1, 1, nx)
+    lbd = net.T - t
+    s = net.smoothing_function(lbd)
+    tau = net.t_encoder(net.get_pis_timestep_embedding(lbd))
+    with torch.no_grad():
+        cf = torch.exp(-0.5 * lbd)
+        res = plan.equation.g(cf * x)
+        res_x = None if value_only else cf * plan.equation.g_x(cf * x)
+    sp, q = _PISCore.apply(plan, not value_only, tau, x, *plan.params)
+    w = _weight(tx, beta)
+    u = s * sp + (1.0 - s) * res
+    v_loss = torch.mean(w * loss_fn(u - y[:, :1]), dim=0)
+    if value_only:
+        return v_loss, {}
+    u_x = s * q + (1.0 - s) * res_x
+    g_loss = torch.mean(w * loss_fn(u_x - y[:, 1:1 + nx]), dim=0)
+    loss, info = scaler.scale(v_loss, g_loss)
+    info["train_value_loss"] = v_loss
+    return loss, info
+
+
 def device_objective(beta, loss_fn, scaler, nx):
     """The device form of `value_objective` (scaler None, or a FixedLossScaler of weight <= 1e-9) and of
     `gradient_objective` with a FixedLossScaler: loss and parameter gradients from the HIP kernels of
     csrc/dpi_fit.h, same signature and `info` keys.  The optimizer stays torch's:
-    `loss.sum().backward()` delivers the gradients the forward launch computed."""
+    `loss.sum().backward()` delivers the gradients the forward launch computed.  The network decides at
+    the first batch: a construct_mlp value network takes `_DeviceFit` (loss and gradients in two launches),
+    a PISGradNet takes `_pis_objective` (nn_module in HIP through `_PISCore`, the rest in torch)."""
     from . import _lib
     if scaler is not None and not isinstance(scaler, FixedLossScaler):
         raise NotImplementedError(f"TRAIN.BACKEND: hip with {type(scaler).__name__}: FixedLossScaler only")
@@ -330,7 +475,9 @@ def device_objective(beta, loss_fn, scaler, nx):
     def objective(net, tx, y):
         plan = plans.get(id(net))
         if plan is None or plan.net is not net:
-            plan = plans[id(net)] = _DevicePlan(net, nx)
+            plan = plans[id(net)] = (_PISPlan if type(net).__name__ == "PISGradNet" else _DevicePlan)(net, nx)
+        if isinstance(plan, _PISPlan):
+            return _pis_objective(plan, tx, y, beta, loss_fn, scaler, value_only)
         total, parts = _DeviceFit.apply(plan, tx, y, beta, loss_kind, clip, 0.0 if value_only else c, *plan.params)
         if value_only:
             return total, {}

@@ -434,6 +434,32 @@ int dpi_fit_gradients(int n_in, int n_hidden, const int* widths, int act, const 
                       int y_stride, int B, float beta, int loss_kind, float clip, float c, float* losses, void* ws,
                       size_t ws_bytes, void* stream);
 
+/* --- PISGradNet's nn_module as a differentiable primitive for the fit (additions within ABI 8).
+ * PISGradNet (picard/solution.py:138-289) is u = s(t) sp + (1 - s(t)) g0(c x) with
+ * sp = sum_k N_k(tau, x) x_k, N = nn_module, tau = t_encoder(emb(T - t)) (64 wide).  The time networks,
+ * the g0 part and the loss stay with the caller; these entries compute, per batch row,
+ *   forward:   sp = x . N(tau, x)  and  q = d sp / d x = N + (J^T x)[x columns], J the Jacobian of N;
+ *   backward:  from the cotangents e = d loss / d sp (B) and r = d loss / d q (B, nx; NULL when q was
+ *              not formed) the gradients of loss wrt every weight and bias of nn_module and wrt tau.
+ * Net: n_hidden 1..4 ELU (alpha = 1) hidden layers each 1..512 wide, nx <= 128 (more:
+ * DPI_ERR_UNSUPPORTED), 64 + nx inputs, nx outputs.  W, b, dW, db: host tables of n_hidden + 1 device
+ * pointers as for dpi_fit_gradients; the gradients and dtau (B, 64) are overwritten, never accumulated
+ * into.  tau (B rows of tau_stride >= 64 floats), x (B rows of x_stride >= nx floats), sp (B), q
+ * (B, nx), e (B), r (B, nx) are fp32 on the device, the last four contiguous.  q == NULL: only sp is
+ * formed (the plain value fit) and the backward call takes r == NULL; r != NULL needs a forward call
+ * that formed q.  The state between the two calls lives in ws, which the caller leaves untouched from
+ * the forward call to its backward call: 4-byte aligned, >= dpi_fit_core_workspace_bytes(nx, n_hidden,
+ * widths, B) bytes (0 for a shape the calls refuse), else DPI_ERR_WORKSPACE.  Exact fp32, every sum
+ * over the batch in a fixed order: bitwise reproducible.  One launch (forward) and two (backward) on
+ * `stream`.  Arguments are checked before any device work; B = 0 launches nothing. */
+size_t dpi_fit_core_workspace_bytes(int nx, int n_hidden, const int* widths, int B);
+int dpi_fit_core_forward(int nx, int n_hidden, const int* widths, const float* const* W, const float* const* b,
+                         const float* tau, int tau_stride, const float* x, int x_stride, int B, float* sp,
+                         float* q, void* ws, size_t ws_bytes, void* stream);
+int dpi_fit_core_backward(int nx, int n_hidden, const int* widths, const float* const* W, const float* const* b,
+                          float* const* dW, float* const* db, const float* e, const float* r, int B,
+                          float* dtau, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2,13 +2,15 @@
 (DESIGN.md §5.1): the device objective (TRAIN.BACKEND: hip, csrc/dpi_fit.h) and the torch objective it
 bypasses, in one process on one device, alternating, PAIRS runs each.
 
-Two shapes: the shipped Burgers fit (B = 512, nx = 100, 4 x 128 ELU, c = 1) and the shape of the r03c
-`picard train` log (B = 128, nx = 8, [32, 32] ELU, c = 0.1).  Per run: warm-up steps, then REPS steps each
+Four shapes: the shipped Burgers fit (B = 512, nx = 100, 4 x 128 ELU, c = 1), the shape of the r03c
+`picard train` log (B = 128, nx = 8, [32, 32] ELU, c = 0.1), and two PISGradNet fits on an OUProcessEquation with
+a seeded two-component mixture: the HJB YAML's (B = 512, nx = 100, [512] * 4, c = 0.1) and the nest YAML's
+(B = 512, nx = 10, [64] * 4, c = 1).  Per run: warm-up steps, then REPS steps each
 bracketed by its own pair of HIP events; the median is reported (ms/step) with the minimum beside it.  One
 JSON line per run, then one per shape with the acceptance figures of the project's protocol (§2.1): every
 device run below every torch run, and the gain against 3 x the spread of the torch runs.
 
-    python tools/time_fit.py [--reps 30] [--warmup 5] [--pairs 3]
+    python tools/time_fit.py [--reps 30] [--warmup 5] [--pairs 3] [--only SUBSTRING]
 """
 import argparse
 import json
@@ -22,12 +24,23 @@ import deeppicarditeration_amd as dpi  # noqa: E402
 from deeppicarditeration_amd import fit  # noqa: E402
 
 SHAPES = [("burgers B512 nx100 4x128 ELU c1", 512, 100, [128] * 4, 1.0),
-          ("r03c B128 nx8 2x32 ELU c0.1", 128, 8, [32, 32], 0.1)]
+          ("r03c B128 nx8 2x32 ELU c0.1", 128, 8, [32, 32], 0.1),
+          ("hjb pisgradnet B512 nx100 4x512 c0.1", 512, 100, [512] * 4, 0.1),
+          ("nest pisgradnet B512 nx10 4x64 c1", 512, 10, [64] * 4, 1.0)]
 
 
-def time_steps(backend, B, nx, widths, c, reps, warmup):
+def make_net(name, nx, widths):
+    if "pisgradnet" not in name:
+        return dpi.construct_mlp(1 + nx, 1, widths, ["ELU"] * len(widths), None)
+    eq = dpi.OUProcessEquation(nx=nx, T=1.0, num_components=2, mean=torch.randn(2, nx, dtype=torch.float64),
+                               var=2.0 * torch.ones(2, nx, dtype=torch.float64),
+                               pi=torch.tensor([0.4, 0.6], dtype=torch.float64))
+    return dpi.PISGradNet(hidden_shapes=list(widths), dim=nx, g0=eq.g, T=1.0)
+
+
+def time_steps(name, backend, B, nx, widths, c, reps, warmup):
     torch.manual_seed(0)
-    net = dpi.construct_mlp(1 + nx, 1, widths, ["ELU"] * len(widths), None).to("cuda")
+    net = make_net(name, nx, widths).to("cuda")
     scaler = fit.FixedLossScaler(c)
     objective = (fit.device_objective if backend == "hip" else fit.gradient_objective)(0.0, torch.square, scaler, nx)
     opt = torch.optim.Adam(net.parameters(), lr=1e-3)
@@ -55,13 +68,14 @@ def main():
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--pairs", type=int, default=3)
+    ap.add_argument("--only", default="", help="time the shapes whose name contains this")
     a = ap.parse_args()
     assert a.reps >= 20, "the median of at least 20 steps"
-    for name, B, nx, widths, c in SHAPES:
+    for name, B, nx, widths, c in [s for s in SHAPES if a.only in s[0]]:
         runs = {"hip": [], "torch": []}
         for _ in range(a.pairs):
             for backend in ("hip", "torch"):
-                r = time_steps(backend, B, nx, widths, c, a.reps, a.warmup)
+                r = time_steps(name, backend, B, nx, widths, c, a.reps, a.warmup)
                 runs[backend].append(r["ms_median"])
                 print(json.dumps({"shape": name, "backend": backend, **r}), flush=True)
         spread = max(runs["torch"]) - min(runs["torch"])

@@ -101,6 +101,10 @@ SIGNATURES = {
     "dpi_fit_gradients": (c_int, [c_int, c_int, P(c_int), c_int, P(c_void_p), P(c_void_p), P(c_void_p), P(c_void_p),
                                   c_void_p, c_void_p, c_int, c_int, c_float, c_int, c_float, c_float, c_void_p,
                                   c_void_p, c_size_t, c_void_p]),
+    "dpi_fit_step": (c_int, [c_int, c_int, P(c_int), c_int, P(c_void_p), P(c_void_p), P(c_void_p), P(c_void_p),
+                             P(c_void_p), P(c_void_p), P(c_void_p), P(c_void_p), c_void_p, c_void_p, c_int, c_int,
+                             c_float, c_int, c_float, c_float, c_double, c_double, c_double, c_double, c_double, c_int,
+                             c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     "dpi_fit_core_workspace_bytes": (c_size_t, [c_int, c_int, P(c_int), c_int]),
     "dpi_fit_core_forward": (c_int, [c_int, c_int, P(c_int), P(c_void_p), P(c_void_p), c_void_p, c_int, c_void_p,
                                      c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),

@@ -3,7 +3,8 @@ image): the same default schema, `BASE:` chaining with `NAME` joining (config.py
 `KEY VALUE` command-line overrides (config.py:259-262), so the reference's experiment YAMLs load
 unchanged.  Keys added by this build: under DATA BACKEND ("hip"), SEED, EULER_STEPS,
 POINTS_PER_CALL; TRAIN.BACKEND ("torch": the fit's objectives in PyTorch-ROCm; "hip": loss and
-parameter gradients in the kernels of csrc/dpi_fit.h).
+parameter gradients in the kernels of csrc/dpi_fit.h); TRAIN.FUSED_STEP (false; true, under TRAIN.BACKEND:
+hip: the Adam / AdamW update of every parameter in the launch that forms its gradient, fit.device_step).
 """
 import ast
 import copy
@@ -120,7 +121,7 @@ def get_default_cfg() -> CfgNode:
     C.TRAIN = _N({"BATCH_SIZE": 2048, "N_EPOCHS": 1, "SUPERVISE_GRADIENT": None, "SUPERVISE_HESSIAN": None,
                   "NUM_HESS_SAMPLES": -1,
                   # this build
-                  "BACKEND": "torch"})
+                  "BACKEND": "torch", "FUSED_STEP": False})
     C.TRAIN.LOSS = _N({"beta": 0.0, "use_aux_loss": False, "weight_aux_loss": 0.1})
     C.TRAIN.LOSS.SCALER = _N({"cls": None})
     C.TRAIN.LOSS.SCALER.kwargs = _N(new_allowed=True)
@@ -149,6 +150,28 @@ def get_default_cfg() -> CfgNode:
     C.LOGGING.kwargs = _N({"project": "picard", "offline": False}, new_allowed=True)
     C.EVAL = _N({"L2_N_POINTS": 10_000, "FREQ": None, "BATCH_SIZE": None, "TEST_GRAD": False, "TEST_HESSIAN": False})
     return C
+
+
+def check_fused_step(cfg):
+    """What a configuration itself shows TRAIN.FUSED_STEP cannot serve, refused by name when it is loaded
+    (the optimizer object and the network are checked again at the first batch, fit.device_step)."""
+    if not isinstance(cfg.TRAIN.FUSED_STEP, bool):
+        raise ValueError(f"TRAIN.FUSED_STEP {cfg.TRAIN.FUSED_STEP!r}: true or false")
+    if not cfg.TRAIN.FUSED_STEP:
+        return
+    if cfg.TRAIN.BACKEND != "hip":
+        raise NotImplementedError(f"TRAIN.FUSED_STEP with TRAIN.BACKEND: {cfg.TRAIN.BACKEND}: the fused step is the "
+                                  "HIP fit's (TRAIN.BACKEND: hip)")
+    opt = cfg.TRAIN.OPTIMIZER
+    if opt.cls not in ("Adam", "AdamW"):
+        raise NotImplementedError(f"TRAIN.FUSED_STEP with TRAIN.OPTIMIZER.cls {opt.cls}: Adam or AdamW only")
+    for key in ("amsgrad", "maximize", "capturable", "differentiable", "fused"):
+        if dict(opt.kwargs).get(key):
+            raise NotImplementedError(f"TRAIN.FUSED_STEP with TRAIN.OPTIMIZER.kwargs {key}: the fused step is torch's "
+                                      "plain single-tensor update")
+    if cfg.NETWORK.PISGRADNET:
+        raise NotImplementedError("TRAIN.FUSED_STEP with NETWORK.PISGRADNET: a PISGradNet's time networks are fitted "
+                                  "by torch")
 
 
 def _read_file_only(path):
@@ -189,5 +212,6 @@ def load_cfg(cfg_file: str, override: List[str] = None) -> CfgNode:
             raise ValueError("Both RESERVED_MEMORY and MEMORY.RESERVED are set.")
     if cfg.TRAIN.BACKEND not in ("torch", "hip"):
         raise ValueError(f"TRAIN.BACKEND {cfg.TRAIN.BACKEND!r}: one of 'torch', 'hip'")
+    check_fused_step(cfg)
     cfg.freeze()
     return cfg

@@ -14,6 +14,8 @@
 //                in order (64-row chunks staged in LDS, a chunk sum added to the running total), so
 //                dW and db are bitwise reproducible and never accumulated into.  One more workgroup
 //                sums the tiles' loss partials in tile order and writes `losses`.
+//   k_fit_wgrad_step  the same launch with the Adam / AdamW update of every parameter in its epilogue
+//                (dpi_fit_step): with k_fit_rows one whole training step, in place.
 //
 // Rows of the last tile past B are dead: they load zeros, run like live rows, and their loss terms and
 // seeds are selected to +0; k_fit_wgrad never reads them.
@@ -350,8 +352,50 @@ __global__ __launch_bounds__(FIT_NTH) void k_fit_rows(const FitArgs a) {
   }
 }
 
-// dW_l = sum_rows delta_l lambdabar_{l-1}^T + zbar_l a_{l-1}^T, db_l = sum_rows zbar_l, rows in order
-__global__ __launch_bounds__(256) void k_fit_wgrad(const FitArgs a) {
+// What k_fit_wgrad_step takes beside FitArgs: the Adam state of every parameter (the tables of FitArgs' W
+// and b, which this launch writes) and the step's scalars, each formed on the host in double and rounded
+// once, as torch rounds the Python scalars of its update.
+struct FitAdam {
+  float* mW[FIT_LMAX + 1];  // exp_avg of W_l and b_l at [l - 1]
+  float* mb[FIT_LMAX + 1];
+  float* vW[FIT_LMAX + 1];  // exp_avg_sq
+  float* vb[FIT_LMAX + 1];
+  float omb1, beta2, omb2, eps, wd;  // 1 - beta1, beta2, 1 - beta2
+  float decay;                       // 1 - lr wd
+  float step_size, bc2_sqrt;         // lr / (1 - beta1^step), sqrt(1 - beta2^step)
+  int decoupled;                     // 1: AdamW (w *= decay), 0: Adam with L2 weight decay (g += wd w)
+};
+struct FitStepArgs {
+  FitArgs f;  // dW / db entries may be NULL: the gradient is not stored
+  FitAdam o;
+};
+
+// One parameter's update from its gradient, fp32, in the order of torch's single-tensor Adam.  No two of
+// the operations are contracted into an fma: each rounds on its own, as torch's separate kernels round.
+__device__ __forceinline__ void fit_adam(const FitAdam& o, float g, float* __restrict__ w, float* __restrict__ m,
+                                         float* __restrict__ v) {
+#pragma clang fp contract(off)
+  float wv = *w, mv = *m, vv = *v;
+  if (o.wd != 0.f) {
+    if (o.decoupled)
+      wv *= o.decay;
+    else
+      g += o.wd * wv;
+  }
+  mv += (g - mv) * o.omb1;
+  vv = o.beta2 * vv + o.omb2 * g * g;
+  wv -= o.step_size * (mv / (sqrtf(vv) / o.bc2_sqrt + o.eps));
+  *w = wv;
+  *m = mv;
+  *v = vv;
+}
+
+// dW_l = sum_rows delta_l lambdabar_{l-1}^T + zbar_l a_{l-1}^T, db_l = sum_rows zbar_l, rows in order.
+// STEP: the thread that holds the final total of a gradient element also applies the Adam update of its
+// parameter (o, else unused); nothing in this launch reads the weights, k_fit_rows before it is their only
+// reader.
+template <bool STEP>
+__device__ __forceinline__ void fit_wgrad(const FitArgs& a, const FitAdam* o) {
   __shared__ float sD[FIT_WT][FIT_CS], sZ[FIT_WT][FIT_CS], sLB[FIT_WT][FIT_CS], sA[FIT_WT][FIT_CS];
   __shared__ double sl[FIT_LDSW];
   const int tid = threadIdx.x;
@@ -375,7 +419,8 @@ __global__ __launch_bounds__(256) void k_fit_wgrad(const FitArgs a) {
     if (tid == 1) {  // db of the output layer: the sum of the seeds e
       double se = 0.0;
       for (int t = 0; t < a.tiles; ++t) se += part[(size_t)t * (n0 + 1) + n0];
-      a.db[L][0] = (float)se;
+      if (!STEP || a.db[L]) a.db[L][0] = (float)se;
+      if (STEP) fit_adam(*o, (float)se, const_cast<float*>(a.b[L]), o->mb[L], o->vb[L]);
     }
     if (tid == 0) {
       double g = 0.0;
@@ -439,9 +484,20 @@ __global__ __launch_bounds__(256) void k_fit_wgrad(const FitArgs a) {
     btot += bc0 + bc1;
   }
   const int j = j0 + tj, i = i0 + ti;
-  if (j < nout && i < nin) a.dW[l - 1][(size_t)j * nin + i] = (float)tot;
-  if (bias && j < nout) a.db[l - 1][j] = (float)btot;
+  if (j < nout && i < nin) {
+    const size_t e = (size_t)j * nin + i;
+    if (!STEP || a.dW[l - 1]) a.dW[l - 1][e] = (float)tot;
+    if (STEP) fit_adam(*o, (float)tot, const_cast<float*>(a.W[l - 1]) + e, o->mW[l - 1] + e, o->vW[l - 1] + e);
+  }
+  if (bias && j < nout) {
+    if (!STEP || a.db[l - 1]) a.db[l - 1][j] = (float)btot;
+    if (STEP) fit_adam(*o, (float)btot, const_cast<float*>(a.b[l - 1]) + j, o->mb[l - 1] + j, o->vb[l - 1] + j);
+  }
 }
+
+__global__ __launch_bounds__(256) void k_fit_wgrad(const FitArgs a) { fit_wgrad<false>(a, nullptr); }
+// the whole training step's second launch (dpi_fit_step)
+__global__ __launch_bounds__(256) void k_fit_wgrad_step(const FitStepArgs a) { fit_wgrad<true>(a.f, &a.o); }
 
 // ---- PISGradNet's nn_module as a differentiable primitive ("The PISGradNet core") ----
 //

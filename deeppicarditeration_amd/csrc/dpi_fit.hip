@@ -1,4 +1,4 @@
-// C ABI of the fit's device path (include/dpi.h: dpi_fit_workspace_bytes, dpi_fit_gradients for
+// C ABI of the fit's device path (include/dpi.h: dpi_fit_workspace_bytes, dpi_fit_gradients, dpi_fit_step for
 // construct_mlp value networks; dpi_fit_core_workspace_bytes, dpi_fit_core_forward, dpi_fit_core_backward
 // for PISGradNet's nn_module); the kernels are in dpi_fit.h.  Not a row of the unit table: nothing here
 // depends on a (problem, network) route.
@@ -201,40 +201,46 @@ extern "C" size_t dpi_fit_workspace_bytes(int n_in, int n_hidden, const int* wid
   return fit_layout(a) * sizeof(float);
 }
 
-extern "C" int dpi_fit_gradients(int n_in, int n_hidden, const int* widths, int act, const float* const* W,
-                                 const float* const* b, float* const* dW, float* const* db, const float* tx,
-                                 const float* y, int y_stride, int B, float beta, int loss_kind, float clip,
-                                 float c, float* losses, void* ws, size_t ws_bytes, void* stream) {
+namespace {
+
+// what dpi_fit_gradients and dpi_fit_step check and fill, as `who`: 0 with `a` ready to launch and `blk` the
+// weight-gradient workgroups (the losses workgroup not counted), 1 for an empty batch, or the code with the
+// text set.  grads_optional: dW and db may be NULL as whole tables (their entries of `a` are then NULL).
+int fit_begin(FitArgs& a, int& blk, const char* who, bool grads_optional, int n_in, int n_hidden, const int* widths,
+              int act, const float* const* W, const float* const* b, float* const* dW, float* const* db,
+              const float* tx, const float* y, int y_stride, int B, float beta, int loss_kind, float clip, float c,
+              float* losses, void* ws, size_t ws_bytes) {
+  const std::string w(who);
   int rc = fit_shape(n_in, n_hidden, widths, B);
   if (rc) return rc;
   if (act != DPI_ACT_ELU && act != DPI_ACT_TANH)
-    return fail(DPI_ERR_UNSUPPORTED, "fit_gradients: activation " + std::to_string(act) + " (DPI_ACT_ELU or "
+    return fail(DPI_ERR_UNSUPPORTED, w + ": activation " + std::to_string(act) + " (DPI_ACT_ELU or "
                                      "DPI_ACT_TANH for every hidden layer)");
   if (loss_kind != DPI_FIT_LOSS_SQUARE && loss_kind != DPI_FIT_LOSS_CLIP)
-    return fail(DPI_ERR_ARG, "fit_gradients: loss kind (DPI_FIT_LOSS_SQUARE or DPI_FIT_LOSS_CLIP)");
+    return fail(DPI_ERR_ARG, w + ": loss kind (DPI_FIT_LOSS_SQUARE or DPI_FIT_LOSS_CLIP)");
   if (loss_kind == DPI_FIT_LOSS_CLIP && !(clip > 0.f && std::isfinite(clip)))
-    return fail(DPI_ERR_ARG, "fit_gradients: clip must be positive and finite");
+    return fail(DPI_ERR_ARG, w + ": clip must be positive and finite");
   if (!std::isfinite(beta) || !(c >= 0.f) || !std::isfinite(c))
-    return fail(DPI_ERR_ARG, "fit_gradients: beta must be finite and the gradient weight c >= 0 and finite");
-  if (y_stride < n_in) return fail(DPI_ERR_ARG, "fit_gradients: y row stride < 1 + nx");
-  if (B == 0) return 0;
-  if (!W || !b || !dW || !db) return fail(DPI_ERR_ARG, "fit_gradients: null pointer table (W, b, dW, db)");
+    return fail(DPI_ERR_ARG, w + ": beta must be finite and the gradient weight c >= 0 and finite");
+  if (y_stride < n_in) return fail(DPI_ERR_ARG, w + ": y row stride < 1 + nx");
+  if (B == 0) return 1;
+  const bool grads = !(grads_optional && !dW && !db);
+  if (!W || !b || (grads && (!dW || !db))) return fail(DPI_ERR_ARG, w + ": null pointer table (W, b, dW, db)");
   for (int l = 0; l <= n_hidden; ++l)
-    if (!W[l] || !b[l] || !dW[l] || !db[l])
-      return fail(DPI_ERR_ARG, "fit_gradients: null entry in a pointer table at layer " + std::to_string(l));
-  if (!tx || !y || !losses) return fail(DPI_ERR_ARG, "fit_gradients: null tx, y or losses");
-  FitArgs a{};
+    if (!W[l] || !b[l] || (grads && (!dW[l] || !db[l])))
+      return fail(DPI_ERR_ARG, w + ": null entry in a pointer table at layer " + std::to_string(l));
+  if (!tx || !y || !losses) return fail(DPI_ERR_ARG, w + ": null tx, y or losses");
   fit_dims(a, n_in, n_hidden, widths, B);
   const size_t need = fit_layout(a) * sizeof(float);
-  if ((uintptr_t)ws % 8) return fail(DPI_ERR_ARG, "fit_gradients: the workspace must be 8-byte aligned");
+  if ((uintptr_t)ws % 8) return fail(DPI_ERR_ARG, w + ": the workspace must be 8-byte aligned");
   if (!ws || ws_bytes < need)
-    return fail(DPI_ERR_WORKSPACE, "fit_gradients: workspace too small (" + std::to_string(ws_bytes) + " < " +
+    return fail(DPI_ERR_WORKSPACE, w + ": workspace too small (" + std::to_string(ws_bytes) + " < " +
                                    std::to_string(need) + " bytes, dpi_fit_workspace_bytes)");
   for (int l = 0; l <= n_hidden; ++l) {
     a.W[l] = W[l];
     a.b[l] = b[l];
-    a.dW[l] = dW[l];
-    a.db[l] = db[l];
+    a.dW[l] = grads ? dW[l] : nullptr;
+    a.db[l] = grads ? db[l] : nullptr;
   }
   a.tx = tx;
   a.y = y;
@@ -246,19 +252,82 @@ extern "C" int dpi_fit_gradients(int n_in, int n_hidden, const int* widths, int 
   a.c = c;
   a.ws = (float*)ws;
   a.losses = losses;
-  int blk = 0;
+  blk = 0;
   for (int l = 1; l <= n_hidden + 1; ++l) {
     a.blk0[l - 1] = blk;
     blk += ((a.n[l] + FIT_WT - 1) / FIT_WT) * ((a.n[l - 1] + FIT_WT - 1) / FIT_WT);
   }
   a.blk0[n_hidden + 1] = blk;
-  hipStream_t st = (hipStream_t)stream;
+  return 0;
+}
+
+void launch_fit_rows(const FitArgs& a, int act, hipStream_t st) {
   if (act == DPI_ACT_TANH)
     hipLaunchKernelGGL(k_fit_rows<DPI_ACT_TANH>, dim3(a.tiles), dim3(FIT_NTH), 0, st, a);
   else
     hipLaunchKernelGGL(k_fit_rows<DPI_ACT_ELU>, dim3(a.tiles), dim3(FIT_NTH), 0, st, a);
+}
+
+}  // namespace
+
+extern "C" int dpi_fit_gradients(int n_in, int n_hidden, const int* widths, int act, const float* const* W,
+                                 const float* const* b, float* const* dW, float* const* db, const float* tx,
+                                 const float* y, int y_stride, int B, float beta, int loss_kind, float clip,
+                                 float c, float* losses, void* ws, size_t ws_bytes, void* stream) {
+  FitArgs a{};
+  int blk = 0;
+  const int rc = fit_begin(a, blk, "fit_gradients", false, n_in, n_hidden, widths, act, W, b, dW, db, tx, y, y_stride,
+                           B, beta, loss_kind, clip, c, losses, ws, ws_bytes);
+  if (rc) return rc < 0 ? rc : 0;
+  hipStream_t st = (hipStream_t)stream;
+  launch_fit_rows(a, act, st);
   HIPCHK(hipGetLastError());
   hipLaunchKernelGGL(k_fit_wgrad, dim3(blk + 1), dim3(256), 0, st, a);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+extern "C" int dpi_fit_step(int n_in, int n_hidden, const int* widths, int act, float* const* W, float* const* b,
+                            float* const* dW, float* const* db, float* const* mW, float* const* mb,
+                            float* const* vW, float* const* vb, const float* tx, const float* y, int y_stride, int B,
+                            float beta, int loss_kind, float clip, float c, double lr, double beta1, double beta2,
+                            double eps, double weight_decay, int decoupled, int step, float* losses, void* ws,
+                            size_t ws_bytes, void* stream) {
+  if (step < 1) return fail(DPI_ERR_ARG, "fit_step: step " + std::to_string(step) + " < 1 (the 1-based step count)");
+  if (!(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0))
+    return fail(DPI_ERR_ARG, "fit_step: beta1 and beta2 must lie in [0, 1)");
+  if (!(eps >= 0.0) || !std::isfinite(eps)) return fail(DPI_ERR_ARG, "fit_step: eps must be >= 0 and finite");
+  if (!(lr >= 0.0) || !std::isfinite(lr)) return fail(DPI_ERR_ARG, "fit_step: lr must be >= 0 and finite");
+  if (!(weight_decay >= 0.0) || !std::isfinite(weight_decay))
+    return fail(DPI_ERR_ARG, "fit_step: weight_decay must be >= 0 and finite");
+  FitStepArgs s{};
+  int blk = 0;
+  const int rc = fit_begin(s.f, blk, "fit_step", true, n_in, n_hidden, widths, act, W, b, dW, db, tx, y, y_stride, B,
+                           beta, loss_kind, clip, c, losses, ws, ws_bytes);
+  if (rc) return rc < 0 ? rc : 0;
+  if (!mW || !mb || !vW || !vb)
+    return fail(DPI_ERR_ARG, "fit_step: null moment table (exp_avg, exp_avg_sq of W and b)");
+  for (int l = 0; l <= n_hidden; ++l) {
+    if (!mW[l] || !mb[l] || !vW[l] || !vb[l])
+      return fail(DPI_ERR_ARG, "fit_step: null entry in a moment table at layer " + std::to_string(l));
+    s.o.mW[l] = mW[l];
+    s.o.mb[l] = mb[l];
+    s.o.vW[l] = vW[l];
+    s.o.vb[l] = vb[l];
+  }
+  s.o.omb1 = (float)(1.0 - beta1);
+  s.o.beta2 = (float)beta2;
+  s.o.omb2 = (float)(1.0 - beta2);
+  s.o.eps = (float)eps;
+  s.o.wd = (float)weight_decay;
+  s.o.decay = (float)(1.0 - lr * weight_decay);
+  s.o.decoupled = decoupled ? 1 : 0;
+  s.o.step_size = (float)(lr / (1.0 - std::pow(beta1, (double)step)));
+  s.o.bc2_sqrt = (float)std::sqrt(1.0 - std::pow(beta2, (double)step));
+  hipStream_t st = (hipStream_t)stream;
+  launch_fit_rows(s.f, act, st);
+  HIPCHK(hipGetLastError());
+  hipLaunchKernelGGL(k_fit_wgrad_step, dim3(blk + 1), dim3(256), 0, st, s);
   HIPCHK(hipGetLastError());
   return 0;
 }

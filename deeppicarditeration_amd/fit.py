@@ -20,6 +20,8 @@ and the loss, which stay torch's.  The fit consumes the device-resident labels.
 - the loss scalers of solution_jac.py:13-109 and LossFnLinearClip (solution.py:22-33);
 - `device_objective`: `value_objective` and `gradient_objective` (FixedLossScaler) on the device, for
   construct_mlp value networks and for PISGradNet;
+- `device_step` / `fused_train_steps`: under TRAIN.FUSED_STEP the whole training step of a construct_mlp
+  value network (loss, gradients and the Adam / AdamW update) in the same two launches, dpi_fit_step;
 - `build_objective`: the wrapper choice of PicardRunner.get_solution (picard_iteration.py:113-118)
   and PicardSolutionGradientWrapper.construct_solution / __init__ (solution_jac.py:112-136).
 
@@ -275,6 +277,25 @@ class _DevicePlan:
         return (_lib.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
 
 
+def _device_batch(plan, tx, y):
+    """What both device calls of a construct_mlp fit need of one batch: the loaded library, tx and y as the
+    kernels read them, B, the plan's workspace grown to the batch and a fresh `losses` (2 + nx,)."""
+    from . import _lib
+    lib = _lib.load()
+    if tx.device.type != "cuda":
+        raise _lib.DPIError("TRAIN.BACKEND: hip needs the batch on the GPU (there is no CPU fallback)")
+    if tx.dtype != torch.float32 or y.dtype != torch.float32:
+        raise NotImplementedError(f"TRAIN.BACKEND: hip with {tx.dtype} batches: fp32 only (DATA.FLOAT: float)")
+    tx, y = tx.detach().contiguous(), y.detach()
+    if y.stride(-1) != 1:
+        y = y.contiguous()
+    B = int(tx.shape[0])
+    need = int(lib.dpi_fit_workspace_bytes(plan.n_in, plan.n_hidden, plan.widths, B))
+    if plan.ws is None or plan.ws.numel() < need or plan.ws.device != tx.device:
+        plan.ws = torch.empty(max(need, 1), dtype=torch.uint8, device=tx.device)
+    return lib, tx, y, B, torch.empty(1 + plan.n_in, dtype=torch.float32, device=tx.device)
+
+
 class _DeviceFit(torch.autograd.Function):
     """losses (2 + nx,) = (total, v_loss, g_loss[nx]) of one batch from dpi_fit_gradients, launched on
     torch's current stream; the parameter gradients it computed are kept and handed to the parameters
@@ -283,20 +304,8 @@ class _DeviceFit(torch.autograd.Function):
     @staticmethod
     def forward(ctx, plan, tx, y, beta, loss_kind, clip, c, *params):
         from . import _lib
-        lib = _lib.load()
-        if tx.device.type != "cuda":
-            raise _lib.DPIError("TRAIN.BACKEND: hip needs the batch on the GPU (there is no CPU fallback)")
-        if tx.dtype != torch.float32 or y.dtype != torch.float32:
-            raise NotImplementedError(f"TRAIN.BACKEND: hip with {tx.dtype} batches: fp32 only (DATA.FLOAT: float)")
-        tx, y = tx.detach().contiguous(), y.detach()
-        if y.stride(-1) != 1:
-            y = y.contiguous()
-        B, nx = int(tx.shape[0]), plan.n_in - 1
-        need = int(lib.dpi_fit_workspace_bytes(plan.n_in, plan.n_hidden, plan.widths, B))
-        if plan.ws is None or plan.ws.numel() < need or plan.ws.device != tx.device:
-            plan.ws = torch.empty(max(need, 1), dtype=torch.uint8, device=tx.device)
+        lib, tx, y, B, losses = _device_batch(plan, tx, y)
         grads = [torch.empty_like(p) for p in params]
-        losses = torch.empty(2 + nx, dtype=torch.float32, device=tx.device)
         _lib.check(lib.dpi_fit_gradients(plan.n_in, plan.n_hidden, plan.widths, plan.act, plan.table(params[0::2]),
                                          plan.table(params[1::2]), plan.table(grads[0::2]), plan.table(grads[1::2]),
                                          tx.data_ptr(), y.data_ptr(), int(y.stride(0)), B, float(beta), loss_kind,
@@ -452,13 +461,9 @@ def _pis_objective(plan, tx, y, beta, loss_fn, scaler, value_only):
     return loss, info
 
 
-def device_objective(beta, loss_fn, scaler, nx):
-    """The device form of `value_objective` (scaler None, or a FixedLossScaler of weight <= 1e-9) and of
-    `gradient_objective` with a FixedLossScaler: loss and parameter gradients from the HIP kernels of
-    csrc/dpi_fit.h (DESIGN.md §5.1), same signature and `info` keys.  The optimizer stays torch's:
-    `loss.sum().backward()` delivers the gradients the forward launch computed.  The network decides at
-    the first batch: a construct_mlp value network takes `_DeviceFit` (loss and gradients in two launches),
-    a PISGradNet takes `_pis_objective` (nn_module in HIP through `_PISCore`, the rest in torch)."""
+def _device_loss_args(loss_fn, scaler):
+    """(loss_kind, clip, c, value_only) of the C calls from the loss function and the scaler; what the kernels
+    do not have is refused by name."""
     from . import _lib
     if scaler is not None and not isinstance(scaler, FixedLossScaler):
         raise NotImplementedError(f"TRAIN.BACKEND: hip with {type(scaler).__name__}: FixedLossScaler only")
@@ -469,7 +474,17 @@ def device_objective(beta, loss_fn, scaler, nx):
     else:
         raise NotImplementedError(f"TRAIN.BACKEND: hip with the loss function {loss_fn!r}: the square or LossFnLinearClip")
     c = 0.0 if scaler is None else float(scaler.fixed_weight)
-    value_only = c <= 1e-9
+    return loss_kind, clip, c, c <= 1e-9
+
+
+def device_objective(beta, loss_fn, scaler, nx):
+    """The device form of `value_objective` (scaler None, or a FixedLossScaler of weight <= 1e-9) and of
+    `gradient_objective` with a FixedLossScaler: loss and parameter gradients from the HIP kernels of
+    csrc/dpi_fit.h (DESIGN.md §5.1), same signature and `info` keys.  The optimizer stays torch's:
+    `loss.sum().backward()` delivers the gradients the forward launch computed.  The network decides at
+    the first batch: a construct_mlp value network takes `_DeviceFit` (loss and gradients in two launches),
+    a PISGradNet takes `_pis_objective` (nn_module in HIP through `_PISCore`, the rest in torch)."""
+    loss_kind, clip, c, value_only = _device_loss_args(loss_fn, scaler)
     plans = {}
 
     def objective(net, tx, y):
@@ -486,6 +501,103 @@ def device_objective(beta, loss_fn, scaler, nx):
     return objective
 
 
+FUSED_OPTIMIZERS = ("Adam", "AdamW")  # TRAIN.FUSED_STEP: the updates k_fit_wgrad_step applies
+
+
+def _fused_group(opt, plan):
+    """The single param group of `opt` as the fused step reads it on every step, checked: torch.optim.Adam
+    or AdamW itself over exactly the plan's parameters, in torch's plain single-tensor arithmetic."""
+    if type(opt) not in (torch.optim.Adam, torch.optim.AdamW):
+        raise NotImplementedError(f"TRAIN.FUSED_STEP with TRAIN.OPTIMIZER.cls {type(opt).__name__}: "
+                                  f"{' or '.join(FUSED_OPTIMIZERS)} only")
+    if len(opt.param_groups) != 1:
+        raise NotImplementedError(f"TRAIN.FUSED_STEP with {len(opt.param_groups)} param groups: one param group only")
+    group = opt.param_groups[0]
+    for key in ("amsgrad", "maximize", "capturable", "differentiable", "fused"):
+        if group.get(key):
+            raise NotImplementedError(f"TRAIN.FUSED_STEP with TRAIN.OPTIMIZER.kwargs {key}: the fused step is torch's "
+                                      "plain single-tensor update")
+    if isinstance(group["lr"], torch.Tensor) or any(isinstance(b, torch.Tensor) for b in group["betas"]):
+        raise NotImplementedError("TRAIN.FUSED_STEP with a tensor lr or tensor betas: the step size is formed on the "
+                                  "host from floats")
+    if sorted(map(id, group["params"])) != sorted(map(id, plan.params)):
+        raise NotImplementedError("TRAIN.FUSED_STEP with a param group that is not exactly the network's parameters")
+    return group
+
+
+def _fused_state(opt, plan):
+    """opt.state of every parameter of the plan, created where it is missing the way torch's Adam creates it at
+    its first step (`step` a CPU scalar tensor, the moments zeros like the parameter); the step
+    counters must agree, as they do after any number of steps of either form."""
+    states = []
+    for p in plan.params:
+        st = opt.state[p]
+        if len(st) == 0:
+            st["step"] = torch.tensor(0.0, dtype=(torch.float64 if torch.get_default_dtype() == torch.float64
+                                                  else torch.float32))
+            st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+            st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+        for key in ("exp_avg", "exp_avg_sq"):
+            m = st[key]
+            if m.dtype != torch.float32 or not m.is_contiguous() or m.shape != p.shape or m.device != p.device:
+                raise NotImplementedError(f"TRAIN.FUSED_STEP with an optimizer state {key} that is not an fp32 contiguous "
+                                          "tensor like its parameter")
+        states.append(st)
+    if len({float(st["step"]) for st in states}) != 1:
+        raise NotImplementedError("TRAIN.FUSED_STEP with parameters at different optimizer step counts")
+    return states
+
+
+def device_step(beta, loss_fn, scaler, nx):
+    """One whole training step on the device (TRAIN.FUSED_STEP under TRAIN.BACKEND: hip):
+    `step(net, opt, tx, y) -> losses (2 + nx,)` = (total, v_loss, g_loss[nx]) of the batch, formed before the
+    update, from dpi_fit_step: k_fit_rows and k_fit_wgrad_step compute the loss and the gradients and apply
+    the Adam / AdamW update of every parameter in the same two launches, with no autograd and no gradient
+    tensors: `p.grad` stays None.  `opt` is the torch.optim.Adam / AdamW `make_optimizer` builds: lr, betas,
+    eps and weight_decay are read from its one param group on every step (so host-side schedulers keep
+    working), the moments and the counter live in `opt.state` in torch's layout (so `opt.state_dict()` is
+    torch's and a run may switch between the two step forms).  Same options as `device_objective`; an
+    optimizer or network the kernel does not cover is refused by name at the first batch, before the library
+    is touched.  There is no fallback."""
+    loss_kind, clip, c, value_only = _device_loss_args(loss_fn, scaler)
+    plans = {}
+
+    def step(net, opt, tx, y):
+        plan = plans.get(id(net))
+        if plan is None or plan.net is not net:
+            if type(net).__name__ == "PISGradNet":
+                raise NotImplementedError("TRAIN.FUSED_STEP with NETWORK.PISGRADNET (a PISGradNet): its time networks "
+                                          "are fitted by torch")
+            plan = plans[id(net)] = _DevicePlan(net, nx)
+        group = _fused_group(opt, plan)
+        states = _fused_state(opt, plan)
+        from . import _lib
+        lib, tx, y, B, losses = _device_batch(plan, tx, y)
+        t = int(states[0]["step"]) + 1
+        b1, b2 = group["betas"]
+        decoupled = isinstance(opt, torch.optim.AdamW) or bool(group.get("decoupled_weight_decay"))
+        m, v = [st["exp_avg"] for st in states], [st["exp_avg_sq"] for st in states]
+        _lib.check(lib.dpi_fit_step(plan.n_in, plan.n_hidden, plan.widths, plan.act, plan.table(plan.params[0::2]),
+                                    plan.table(plan.params[1::2]), None, None, plan.table(m[0::2]), plan.table(m[1::2]),
+                                    plan.table(v[0::2]), plan.table(v[1::2]), tx.data_ptr(), y.data_ptr(),
+                                    int(y.stride(0)), B, float(beta), loss_kind, float(clip),
+                                    0.0 if value_only else float(c), float(group["lr"]), float(b1), float(b2),
+                                    float(group["eps"]), float(group["weight_decay"]), int(decoupled), t,
+                                    losses.data_ptr(), plan.ws.data_ptr(), plan.ws.numel(),
+                                    torch.cuda.current_stream(tx.device).cuda_stream), "dpi_fit_step")
+        for st in states:
+            st["step"] += 1
+        return losses
+    return step
+
+
+def step_info(losses, value_only=False):
+    """The `info` of `device_objective` from the losses (2 + nx,) of one fused step."""
+    if value_only:
+        return {}
+    return {"train_gradient_loss(unscaled)": losses[2:].sum(dim=-1, keepdim=True), "train_value_loss": losses[1:2]}
+
+
 def make_scaler(scaler_cfg):
     """solution_jac.py:132-136: no SCALER.cls means FixedLossScaler(1.0)."""
     if scaler_cfg is None or scaler_cfg.get("cls") is None:
@@ -493,18 +605,25 @@ def make_scaler(scaler_cfg):
     return LossScaler.get_class(scaler_cfg["cls"])(**dict(scaler_cfg.get("kwargs") or {}))
 
 
-def build_objective(train_cfg, nx, supervise_gradient, supervise_hessian, output_dim=1, backend="torch"):
+def build_objective(train_cfg, nx, supervise_gradient, supervise_hessian, output_dim=1, backend="torch",
+                    fused_step=False):
     """PicardRunner.get_solution (picard_iteration.py:113-118) + the wrappers' construct_solution
     (solution_jac.py:112-119): returns (objective, kind) with kind in {"value", "gradient",
     "gradient_hessian", "head_value_gradient", "head_only_gradient"}.  output_dim: the network's
     output width (1: a Value net; 1 + nx / nx: a ValueGradient / OnlyGradient head).  A
     FixedLossScaler of weight <= 1e-9 falls back to the plain value fit (Value nets).
     backend (TRAIN.BACKEND): "torch" builds the objectives above; "hip" builds `device_objective` for the
-    kinds "value" and "gradient" with FixedLossScaler and refuses every other option by name."""
+    kinds "value" and "gradient" with FixedLossScaler and refuses every other option by name.
+    fused_step (TRAIN.FUSED_STEP, "hip" only): what is returned in the objective's place is the `device_step`
+    of the same options, for `fused_train_steps`."""
     if backend not in BACKENDS:
         raise ValueError(f"TRAIN.BACKEND {backend!r}: one of {BACKENDS}")
+    if fused_step and backend != "hip":
+        raise NotImplementedError(f"TRAIN.FUSED_STEP with TRAIN.BACKEND: {backend}: the fused step is the HIP fit's "
+                                  "(TRAIN.BACKEND: hip)")
     if backend == "hip":
-        return _build_device_objective(train_cfg, nx, supervise_gradient, supervise_hessian, output_dim)
+        return _build_device_objective(train_cfg, nx, supervise_gradient, supervise_hessian, output_dim,
+                                       device_step if fused_step else device_objective)
     loss_cfg = train_cfg["LOSS"]
     beta = float(loss_cfg["beta"])
     loss_fn = make_loss_fn(loss_cfg.get("FN"))
@@ -542,9 +661,10 @@ def build_objective(train_cfg, nx, supervise_gradient, supervise_hessian, output
     return gradient_objective(beta, loss_fn, scaler, nx), "gradient"
 
 
-def _build_device_objective(train_cfg, nx, supervise_gradient, supervise_hessian, output_dim):
+def _build_device_objective(train_cfg, nx, supervise_gradient, supervise_hessian, output_dim, make):
     """build_objective under TRAIN.BACKEND: hip.  The options the fit kernels do not cover raise
-    NotImplementedError naming the option; the network itself is checked at the first batch."""
+    NotImplementedError naming the option; the network itself is checked at the first batch.
+    make: `device_objective`, or `device_step` under TRAIN.FUSED_STEP."""
     loss_cfg = train_cfg["LOSS"]
     beta = float(loss_cfg["beta"])
     loss_fn = make_loss_fn(loss_cfg.get("FN"))
@@ -555,7 +675,7 @@ def _build_device_objective(train_cfg, nx, supervise_gradient, supervise_hessian
         raise NotImplementedError("TRAIN.BACKEND: hip with TRAIN.SUPERVISE_HESSIAN: the fit kernels have the value "
                                   "and gradient losses only")
     if not supervise_gradient:
-        return device_objective(beta, loss_fn, None, nx), "value"
+        return make(beta, loss_fn, None, nx), "value"
     if bool(loss_cfg.get("use_aux_loss")):
         raise NotImplementedError("TRAIN.LOSS.use_aux_loss applies to ValueGradient networks only")
     scaler = make_scaler(loss_cfg.get("SCALER"))
@@ -563,7 +683,7 @@ def _build_device_objective(train_cfg, nx, supervise_gradient, supervise_hessian
         raise NotImplementedError(f"TRAIN.BACKEND: hip with TRAIN.LOSS.SCALER {type(scaler).__name__}: "
                                   "FixedLossScaler only")
     kind = "value" if scaler.fixed_weight <= 1e-9 else "gradient"
-    return device_objective(beta, loss_fn, scaler, nx), kind
+    return make(beta, loss_fn, scaler, nx), kind
 
 
 def make_optimizer(params, opt_cfg):
@@ -598,3 +718,20 @@ def train_steps(net, objective, opt, batches, sched=None):
                 sched.step()
         losses.append(loss.detach().reshape(()))
     return torch.stack(losses) if losses else torch.empty(0)
+
+
+def fused_train_steps(net, step, opt, batches, sched=None):
+    """`train_steps` under TRAIN.FUSED_STEP: one `device_step` call per (tx, y) batch in place of objective,
+    zero_grad, backward and opt.step, then the step-interval scheduler as there.  Returns the per-step
+    total losses as a device tensor (no host synchronisation per step); the `info` of a step is
+    `step_info` of the losses `step` returns.  No gradient tensor exists: `p.grad` stays None."""
+    rows = []
+    for tx, y in batches:
+        losses = step(net, opt, tx, y)
+        if sched is not None:
+            if isinstance(sched, torch.optim.lr_scheduler.ReduceLROnPlateau):
+                sched.step(losses[0])
+            else:
+                sched.step()
+        rows.append(losses)
+    return torch.stack(rows)[:, 0] if rows else torch.empty(0)

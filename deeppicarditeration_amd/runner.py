@@ -27,7 +27,7 @@ from . import equations as eqs
 from .config import CfgNode
 from .data import OnlineDataGenerator
 from .dataset import TensorDatasetBuiltInShuffle
-from .fit import build_objective, make_optimizer, train_steps
+from .fit import build_objective, fused_train_steps, make_optimizer, train_steps
 from .sharding import ShardedLabeler
 from .solution import (OUTPUT_DIM, TERMINAL_CLS, TERMINAL_HEADS, PicardSolutionEnforceTerminal, PISGradNet, ZeroSolution,
                        construct_mlp, head_columns)
@@ -228,9 +228,13 @@ class PicardRunner:
         module, the first epoch takes the labels in the order they were drawn and later epochs
         replay the in-memory cache, shuffled when DATA.SHUFFLE is set (dataset.py:203-255)."""
         t = self.cfg.TRAIN
+        # TRAIN.FUSED_STEP: `objective` is fit.device_step and a step is one dpi_fit_step call
+        fused = bool(t.get("FUSED_STEP", False))
         objective, self.fit_kind = build_objective(t, self.equation.nx, self.supervise_gradient,
                                                    self.supervise_hessian, self.output_dim,
-                                                   backend=str(t.get("BACKEND", "torch")))
+                                                   backend=str(t.get("BACKEND", "torch")), fused_step=fused)
+        steps = fused_train_steps if fused else train_steps
+        self.fit_step = "fused" if fused else "torch"
         opt, sched = make_optimizer(net.parameters(), t.OPTIMIZER)
         n = tx.shape[0]
         bs = int(t.BATCH_SIZE) if t.BATCH_SIZE else n
@@ -245,8 +249,8 @@ class PicardRunner:
         for epoch in range(int(t.N_EPOCHS)):
             batches = TensorDatasetBuiltInShuffle(tx, y, batch_size=bs, drop_last=rebatched,
                                                   shuffle=shuffle and (epoch > 0 or rebatched))
-            losses.append(train_steps(net, objective, opt, batches, sched))
-        losses = torch.cat(losses) if losses else torch.empty(0)
+            losses.append(steps(net, objective, opt, batches, sched))
+        losses = self.fit_losses = torch.cat(losses) if losses else torch.empty(0)  # per step, on the device
         return float(losses[-1]) if losses.numel() else float("nan")
 
     # ------------------------------------------------------------------ eval
@@ -348,7 +352,7 @@ class PicardRunner:
         rec = {"iter": self.i, "labels": n, "label_s": t_labels, "labels_per_s": n / t_labels,
                "path_labels_per_s": None if self.cfg.DATA.EXACT else n * M / t_labels, "ranks": self.world,
                "fit_s": t_fit, "fit": self.fit_kind, "fit_backend": str(self.cfg.TRAIN.get("BACKEND", "torch")),
-               "loss": loss, "rel_l2_u": metrics.get("rRMSE"), **metrics}
+               "fit_step": self.fit_step, "loss": loss, "rel_l2_u": metrics.get("rRMSE"), **metrics}
         self.history.append(rec)
         with open(self.exp_dir / "history.jsonl", "a") as f:
             f.write(json.dumps(rec) + "\n")

@@ -33,6 +33,8 @@
  *   dpi_label_moments_hessians / dpi_label_finalize_hessians  the same, split for MC sharding
  *   dpi_sums_reduce          (no reference counterpart: fixed-order combine of per-rank sums)
  *   dpi_set_gemm_precision   (no reference counterpart: MFMA precision of the network evaluation)
+ *   dpi_fit_gradients        picard/solution.py:74-81, picard/solution_jac.py:167-213  training_step + its backward
+ *   dpi_fit_step             the same + picard/solution.py:94-126  the torch.optim.Adam / AdamW step after it
  */
 #ifndef DPI_H_
 #define DPI_H_
@@ -433,6 +435,31 @@ int dpi_fit_gradients(int n_in, int n_hidden, const int* widths, int act, const 
                       const float* const* b, float* const* dW, float* const* db, const float* tx, const float* y,
                       int y_stride, int B, float beta, int loss_kind, float clip, float c, float* losses, void* ws,
                       size_t ws_bytes, void* stream);
+
+/* --- one whole training step of the same fit (an addition within ABI 8).  dpi_fit_gradients' loss and
+ * gradients, and in the launch that finishes them the update torch.optim.Adam / AdamW (single-tensor,
+ * non-capturable; no amsgrad, no maximize) applies to every parameter, in place: per element, in fp32, with
+ * g the fp32 gradient dpi_fit_gradients would have written,
+ *   decoupled == 0 (Adam, L2 weight decay):  g += weight_decay w      decoupled != 0 (AdamW):  w *= 1 - lr weight_decay
+ *   m += (g - m)(1 - beta1);   v = beta2 v + (1 - beta2) g g;   w -= step_size m / (sqrt(v) / bc2_sqrt + eps)
+ * with step_size = lr / (1 - beta1^step) and bc2_sqrt = sqrt(1 - beta2^step) formed on the host in double
+ * (step: the 1-based count of this step; nothing is read back from the device).  lr, beta1, beta2, eps and
+ * weight_decay are doubles, as torch holds them: 1 - beta1, 1 - beta2 and 1 - lr weight_decay are formed in
+ * double too and every scalar the kernel uses is rounded to fp32 once.
+ * Arguments as for dpi_fit_gradients, and: W, b are written; mW, mb (exp_avg) and vW, vb (exp_avg_sq): host
+ * tables of n_hidden + 1 device pointers to fp32 tensors of the parameters' shapes, read and written.  dW
+ * and db may both be NULL as whole tables: the gradients are then not stored; otherwise they receive what
+ * dpi_fit_gradients writes.  `losses` are those of the weights before the update.  Same workspace
+ * (dpi_fit_workspace_bytes), same shape limits, the same two launches on `stream`; no workgroup waits on
+ * another and nothing is accumulated atomically, so losses, moments and weights are bitwise reproducible.
+ * Checked before any device work (DPI_ERR_ARG): step < 1; beta1 or beta2 outside [0, 1); eps, lr or
+ * weight_decay negative or not finite; a NULL moment table or entry; and everything dpi_fit_gradients
+ * checks, with its codes.  B = 0 launches nothing and changes nothing. */
+int dpi_fit_step(int n_in, int n_hidden, const int* widths, int act, float* const* W, float* const* b,
+                 float* const* dW, float* const* db, float* const* mW, float* const* mb, float* const* vW,
+                 float* const* vb, const float* tx, const float* y, int y_stride, int B, float beta, int loss_kind,
+                 float clip, float c, double lr, double beta1, double beta2, double eps, double weight_decay,
+                 int decoupled, int step, float* losses, void* ws, size_t ws_bytes, void* stream);
 
 /* --- PISGradNet's nn_module as a differentiable primitive for the fit (additions within ABI 8).
  * PISGradNet (picard/solution.py:138-289) is u = s(t) sp + (1 - s(t)) g0(c x) with

@@ -11,6 +11,11 @@ JSON line per run, then one per shape with the acceptance figures of the project
 device run below every torch run, and the gain against 3 x the spread of the torch runs.
 
     python tools/time_fit.py [--reps 30] [--warmup 5] [--pairs 3] [--only SUBSTRING]
+
+--step-forms times, by the same protocol, the two forms of a step under TRAIN.BACKEND: hip for the two
+construct_mlp shapes: "fused" (TRAIN.FUSED_STEP: fit.device_step, loss, gradients and the Adam update in
+dpi_fit_step's two launches) against "unfused" (the device objective, backward and torch's Adam), the
+baseline; --form fused|unfused runs that one form alone once per shape (for a kernel trace).
 """
 import argparse
 import json
@@ -42,19 +47,22 @@ def time_steps(name, backend, B, nx, widths, c, reps, warmup):
     torch.manual_seed(0)
     net = make_net(name, nx, widths).to("cuda")
     scaler = fit.FixedLossScaler(c)
-    objective = (fit.device_objective if backend == "hip" else fit.gradient_objective)(0.0, torch.square, scaler, nx)
+    make = {"hip": fit.device_objective, "unfused": fit.device_objective, "fused": fit.device_step,
+            "torch": fit.gradient_objective}[backend]
+    objective = make(0.0, torch.square, scaler, nx)
+    steps = fit.fused_train_steps if backend == "fused" else fit.train_steps
     opt = torch.optim.Adam(net.parameters(), lr=1e-3)
     tx = torch.cat([torch.rand(B, 1), torch.randn(B, nx)], 1).to("cuda")
     y = (torch.randn(B, 1 + nx) * 0.5).to("cuda")
     batch = [(tx, y)]
     for _ in range(warmup):
-        fit.train_steps(net, objective, opt, batch)
+        steps(net, objective, opt, batch)
     torch.cuda.synchronize()
     evs = []
     for _ in range(reps):
         a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         a.record()
-        losses = fit.train_steps(net, objective, opt, batch)
+        losses = steps(net, objective, opt, batch)
         b.record()
         evs.append((a, b))
     torch.cuda.synchronize()
@@ -69,22 +77,30 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--pairs", type=int, default=3)
     ap.add_argument("--only", default="", help="time the shapes whose name contains this")
+    ap.add_argument("--step-forms", action="store_true", help="time the fused step against the unfused hip step")
+    ap.add_argument("--form", choices=("fused", "unfused"), default=None, help="run this step form alone, once")
     a = ap.parse_args()
     assert a.reps >= 20, "the median of at least 20 steps"
-    for name, B, nx, widths, c in [s for s in SHAPES if a.only in s[0]]:
-        runs = {"hip": [], "torch": []}
+    forms = a.step_forms or a.form is not None
+    new, old = ("fused", "unfused") if forms else ("hip", "torch")
+    for name, B, nx, widths, c in [s for s in SHAPES if a.only in s[0] and not (forms and "pisgradnet" in s[0])]:
+        if a.form is not None:
+            r = time_steps(name, a.form, B, nx, widths, c, a.reps, a.warmup)
+            print(json.dumps({"shape": name, "backend": a.form, **r}), flush=True)
+            continue
+        runs = {new: [], old: []}
         for _ in range(a.pairs):
-            for backend in ("hip", "torch"):
+            for backend in (new, old):
                 r = time_steps(name, backend, B, nx, widths, c, a.reps, a.warmup)
                 runs[backend].append(r["ms_median"])
                 print(json.dumps({"shape": name, "backend": backend, **r}), flush=True)
-        spread = max(runs["torch"]) - min(runs["torch"])
-        gain = min(runs["torch"]) - max(runs["hip"])
-        print(json.dumps({"shape": name, "hip_ms": runs["hip"], "torch_ms": runs["torch"],
-                          "every_hip_run_faster": max(runs["hip"]) < min(runs["torch"]), "gain_ms": gain,
-                          "torch_spread_ms": spread, "gain_over_3_spreads": gain > 3 * spread,
-                          "ratio_torch_over_hip": [min(runs["torch"]) / max(runs["hip"]),
-                                                   max(runs["torch"]) / min(runs["hip"])]}), flush=True)
+        spread = max(runs[old]) - min(runs[old])
+        gain = min(runs[old]) - max(runs[new])
+        print(json.dumps({"shape": name, f"{new}_ms": runs[new], f"{old}_ms": runs[old],
+                          f"every_{new}_run_faster": max(runs[new]) < min(runs[old]), "gain_ms": gain,
+                          f"{old}_spread_ms": spread, "gain_over_3_spreads": gain > 3 * spread,
+                          f"ratio_{old}_over_{new}": [min(runs[old]) / max(runs[new]),
+                                                      max(runs[old]) / min(runs[new])]}), flush=True)
 
 
 if __name__ == "__main__":

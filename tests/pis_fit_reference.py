@@ -2,7 +2,9 @@
 four passes of the core primitive (tau, x, nn_module's parameters) -> (sp, q = d sp / d x) and their
 backward, the objective around them, the case table the CPU and GPU tests share, and the torch side of
 the comparison (fit.gradient_objective / fit.value_objective on the whole PISGradNet under autograd).
-No GPU and no library is needed to import this module."""
+For the core alone: its own case table and call forms (CORE_CASES, MODES, core_case), the restatement's direct
+outputs in fp64 or fp32 (core_outputs; the passes run in the dtype of their inputs) and torch autograd of the
+same primitive (torch_core).  No GPU and no library is needed to import this module."""
 import functools
 
 import numpy as np
@@ -40,67 +42,169 @@ IDS = [f"{k}-B{c[0]}-nx{c[1]}-{len(c[2])}x{max(c[2])}-T{c[3]}-b{c[4]}-{'clip' if
        for k, c in enumerate(CASES)]
 NOISE = 0.3  # the labels' distance from the network's own outputs, relative to their rms (make_batch)
 MUTANTS = ("no_tangent", "no_N", "no_v_lambdabar", "no_dtau")
+# mutants of the core alone, each one edge of the kernels (tests/test_pis_core_reference.py): the remainder loop
+# of fit_mv / fit_mvT, k_fit_core_wgrad's unpaired last row, and phi'' on the linear branch of ELU
+CORE_MUTANTS = ("tail_k", "odd_row", "elu2_everywhere")
+
+# The core alone, (B, nx, hidden widths): the shapes at which k_fit_core_fwd / _bwd / _wgrad take another branch
+# or reach a bound.  n0 = 64 + nx is the first layer's row count.
+CORE_CASES = [
+    (1, 3, [16]),              # one row; n0 = 67
+    (65, 1, [3]),              # nx = 1; a width below the 4-unit block; a second tile with one live row
+    (1, 128, [1]),             # width 1 at the nx cap
+    (65, 10, [64] * 4),        # the nest YAML's network
+    (100, 3, [130, 70]),       # no multiple of 4 or 16
+    (129, 127, [17, 511]),     # three tiles, the last with one live row; odd nx, n0 = 191; one unit past a weight
+                               # tile; one under the width cap
+    (64, 128, [512] * 4),      # every cap at once: the LDS vector is full
+    (100, 128, [16]),          # a wide input into one weight-tile row
+    (512, 10, [64] * 2),       # eight tiles
+]
+CORE_IDS = [f"{k}-B{c[0]}-nx{c[1]}-{'x'.join(map(str, c[2]))}" for k, c in enumerate(CORE_CASES)]
+# grad: q formed, e and r given.  value: q NULL, r NULL.  sp_cot_only: q formed, r NULL in the backward.
+# q_cot_only: q formed, e = 0.
+MODES = ("grad", "value", "sp_cot_only", "q_cot_only")
 
 
 def _elu(z):
-    """phi, phi', phi'' of ELU (alpha = 1)."""
-    e = np.exp(np.minimum(z, 0.0))
-    return np.where(z > 0, z, e - 1.0), np.where(z > 0, 1.0, e), np.where(z > 0, 0.0, e)
+    """phi, phi', phi'' of ELU (alpha = 1), in z's dtype."""
+    e = np.exp(np.minimum(z, 0))
+    one, zero = z.dtype.type(1), z.dtype.type(0)
+    return np.where(z > 0, z, e - one), np.where(z > 0, one, e), np.where(z > 0, zero, e)
+
+
+def _mm(a, b, mutant):
+    """a (B, K) @ b (K, N); under tail_k the last K % 4 terms of every sum are dropped (the remainder loop of
+    fit_mv / fit_mvT)."""
+    if mutant == "tail_k":
+        k = a.shape[1] - a.shape[1] % 4
+        return a[:, :k] @ b[:k]
+    return a @ b
 
 
 def core_forward(Ws, bs, tau, x, grad=True, mutant=None):
-    """Passes 1 and 2.  Ws, bs: nn_module's L + 1 layers, (out, in) and (out,); tau (B, 64), x (B, nx).
-    Returns sp (B, 1), q (B, nx) or None, and the state the backward needs."""
+    """Passes 1 and 2, in the dtype of the inputs.  Ws, bs: nn_module's L + 1 layers, (out, in) and (out,);
+    tau (B, 64), x (B, nx).  Returns sp (B, 1), q (B, nx) or None, and the state the backward needs."""
     L = len(Ws) - 1
     a, d1, d2 = [np.concatenate([tau, x], axis=1)], [None], [None]
     for l in range(L):  # 1. forward
-        f, g, h = _elu(a[-1] @ Ws[l].T + bs[l])
+        f, g, h = _elu(_mm(a[-1], Ws[l].T, mutant) + bs[l])
+        if mutant == "elu2_everywhere":
+            h = g
         a.append(f), d1.append(g), d2.append(h)
-    N = a[L] @ Ws[L].T + bs[L]
+    N = _mm(a[L], Ws[L].T, mutant) + bs[L]
     sp = np.sum(x * N, axis=1, keepdims=True)
     st = {"a": a, "d1": d1, "d2": d2, "x": x}
     if not grad:
         return sp, None, st
     lam, delta = [None] * (L + 1), [None] * (L + 1)  # 2. adjoint, delta_{L+1} = v = x
-    lam[L] = x @ Ws[L]
+    lam[L] = _mm(x, Ws[L], mutant)
     for l in range(L, 0, -1):
         delta[l] = lam[l] * d1[l]
-        lam[l - 1] = delta[l] @ Ws[l - 1]
-    q = lam[0][:, NT:] + (0.0 if mutant == "no_N" else N)
+        lam[l - 1] = _mm(delta[l], Ws[l - 1], mutant)
+    q = lam[0][:, NT:] + (0 if mutant == "no_N" else N)
     st.update(lam=lam, delta=delta)
     return sp, q, st
 
 
 def core_backward(Ws, st, e, r, mutant=None):
-    """Passes 3 and 4 from the cotangents e (B, 1) of sp and r (B, nx) of q (None: q was not formed).
-    Returns dWs, dbs and taubar (B, 64)."""
+    """Passes 3 and 4 from the cotangents e (B, 1) of sp and r (B, nx) of q (None: q was not formed, or has
+    no cotangent), in the dtype of the state.  Returns dWs, dbs and taubar (B, 64)."""
     L = len(Ws) - 1
     a, d1, d2, x = st["a"], st["d1"], st["d2"], st["x"]
     B = x.shape[0]
+    rows = slice(0, B - 1) if mutant == "odd_row" and B % 2 else slice(0, B)  # the batch rows dW and db sum
     dWs = [np.zeros_like(W) for W in Ws]
     dbs = [None] * (L + 1)
     zeta = [None] * (L + 1)
     if r is not None and mutant != "no_tangent":  # 3. tangent of the adjoint chain, lambdabar_0 = (0_tau, r)
         lam, delta = st["lam"], st["delta"]
-        lb = np.concatenate([np.zeros((B, NT)), r], axis=1)
+        lb = np.concatenate([np.zeros((B, NT), dtype=r.dtype), r], axis=1)
         for l in range(1, L + 1):
-            db_ = lb @ Ws[l - 1].T
-            dWs[l - 1] += delta[l].T @ lb
+            db_ = _mm(lb, Ws[l - 1].T, mutant)
+            dWs[l - 1] += delta[l][rows].T @ lb[rows]
             lb = db_ * d1[l]
             zeta[l] = db_ * lam[l] * d2[l]
         if mutant != "no_v_lambdabar":
-            dWs[L] += x.T @ lb
-    zb = e * x + (0.0 if r is None else r)  # 4. reverse, zbar_{L+1} = e v + r, down to abar_0
-    dWs[L] += zb.T @ a[L]
-    dbs[L] = zb.sum(axis=0)
-    abar = zb @ Ws[L]
+            dWs[L] += x[rows].T @ lb[rows]
+    zb = e * x + (0 if r is None else r)  # 4. reverse, zbar_{L+1} = e v + r, down to abar_0
+    dWs[L] += zb[rows].T @ a[L][rows]
+    dbs[L] = zb[rows].sum(axis=0)
+    abar = _mm(zb, Ws[L], mutant)
     for l in range(L, 0, -1):
-        zb = abar * d1[l] + (0.0 if zeta[l] is None else zeta[l])
-        dWs[l - 1] += zb.T @ a[l - 1]
-        dbs[l - 1] = zb.sum(axis=0)
-        abar = zb @ Ws[l - 1]
-    taubar = abar[:, :NT] * (0.0 if mutant == "no_dtau" else 1.0)
+        zb = abar * d1[l] + (0 if zeta[l] is None else zeta[l])
+        dWs[l - 1] += zb[rows].T @ a[l - 1][rows]
+        dbs[l - 1] = zb[rows].sum(axis=0)
+        abar = _mm(zb, Ws[l - 1], mutant)
+    taubar = abar[:, :NT] * (0 if mutant == "no_dtau" else 1)
     return dWs, dbs, taubar
+
+
+def core_case(k, mode, seed=0):
+    """fp32 numpy (Ws, bs, tau, x, e, r) of CORE_CASES[k]: W = (U(-1, 1) + N(0, 1)) / sqrt(fan_in), b =
+    U(-1, 1) / sqrt(fan_in) + 0.3 N(0, 1), tau, x, e, r standard normals, drawn in the order returned (every
+    W, the uniform part first; then every b; then the data) whatever the mode, so the modes of a case share
+    their inputs.  r is None where the backward gets none (value, sp_cot_only) and e is zeros under
+    q_cot_only.  The cap of tests/test_pis_core_reference.py (E_case <= 2e-6) is a condition on these very
+    draws: at B = 1, sp is one number, x . N, and a draw in which its nx terms cancel would fail the cap
+    before any kernel is looked at.  Change the draws and the cap has to be checked again."""
+    assert mode in MODES
+    B, nx, widths = CORE_CASES[k]
+    rng = np.random.default_rng(100 + k + 1000 * seed)
+    n = [NT + nx] + list(widths) + [nx]
+    fan = list(zip(n[1:], n[:-1]))
+    Ws = [((rng.uniform(-1, 1, (o, i)) + rng.standard_normal((o, i))) * i ** -0.5).astype(np.float32) for o, i in fan]
+    bs = [(rng.uniform(-1, 1, o) * i ** -0.5 + 0.3 * rng.standard_normal(o)).astype(np.float32) for o, i in fan]
+    tau, x, e, r = (rng.standard_normal((B, m)).astype(np.float32) for m in (NT, nx, 1, nx))
+    if mode == "q_cot_only":
+        e = np.zeros_like(e)
+    if mode in ("value", "sp_cot_only"):
+        r = None
+    return Ws, bs, tau, x, e, r
+
+
+def core_names(k):
+    """The core's outputs in the order core_outputs and torch_core return them."""
+    L1 = len(CORE_CASES[k][2]) + 1
+    return ["sp", "q", "dtau"] + [f"dW{l}" for l in range(1, L1 + 1)] + [f"db{l}" for l in range(1, L1 + 1)]
+
+
+def core_outputs(inputs, mode, dtype=np.float64, mutant=None):
+    """[sp, q or None, taubar, dW_1 .., db_1 ..] of the restatement run in `dtype` on the inputs of core_case."""
+    Ws, bs, tau, x, e, r = [[a.astype(dtype) for a in v] if isinstance(v, list) else
+                            (None if v is None else v.astype(dtype)) for v in inputs]
+    sp, q, st = core_forward(Ws, bs, tau, x, grad=mode != "value", mutant=mutant)
+    dWs, dbs, taubar = core_backward(Ws, st, e, r, mutant=mutant)
+    out = [sp, q, taubar] + dWs + dbs
+    assert all(o is None or o.dtype == dtype for o in out)
+    return out
+
+
+def torch_core(inputs, mode, dtype=torch.float64, device="cpu"):
+    """The same outputs from torch autograd: nn_module rebuilt from Ws and bs, sp = (x N).sum(1), q =
+    grad(sp.sum(), x, create_graph=True), and the cotangent (e sp).sum() + (r q).sum().  fp64 numpy."""
+    t = lambda a: None if a is None else torch.from_numpy(a).to(dtype=dtype, device=device)  # noqa: E731
+    Ws, bs = [t(W).requires_grad_() for W in inputs[0]], [t(b).requires_grad_() for b in inputs[1]]
+    tau, x, e, r = (t(a) for a in inputs[2:])
+    tau.requires_grad_(), x.requires_grad_()
+    h = torch.cat([tau, x], 1)
+    for W, b in zip(Ws[:-1], bs[:-1]):
+        h = torch.nn.functional.elu(torch.nn.functional.linear(h, W, b))
+    sp = (x * torch.nn.functional.linear(h, Ws[-1], bs[-1])).sum(1, keepdim=True)
+    q = None
+    cot = (e * sp).sum()
+    if mode != "value":
+        q, = torch.autograd.grad(sp.sum(), x, create_graph=True)
+        if r is not None:
+            cot = cot + (r * q).sum()
+    grads = torch.autograd.grad(cot, [tau] + Ws + bs)
+    return [None if o is None else o.detach().double().cpu().numpy() for o in (sp, q) + tuple(grads)]
+
+
+def core_errors(got, want):
+    """Per-output rel-L2 against the fp64 outputs; None where the output is not formed or its fp64 value is
+    exactly zero (such an output has to come back exactly zero, which the caller asserts)."""
+    return [None if w is None or not np.any(w) else rel_l2(g, w) for g, w in zip(got, want)]
 
 
 class _NumpyCore(torch.autograd.Function):

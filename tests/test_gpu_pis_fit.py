@@ -6,7 +6,9 @@ semantics of the C calls; a 20-step Adam trajectory; and `picard train` end to e
 
 Measured on an MI355X over the 14 cases of tests/pis_fit_reference.py: e_hip 2.7e-6 - 2.9e-5
 against e_32 2.8e-6 - 2.9e-5, e_hip / e_32 0.69 - 1.11; in both the largest error sits in a time network's
-tensor (smooth_net, t_encoder), which torch computes under either backend.  The trajectory distances are
+tensor (smooth_net, t_encoder), which torch computes under either backend; over nn_module's tensors alone, the
+ones the HIP core computes, e_hip is 1.1e-6 - 1.1e-5 against e_32 1.2e-6 - 1.3e-5, ratio 0.64 - 1.11 (the core's
+outputs themselves are held to fp64 in tests/test_gpu_pis_core.py).  The trajectory distances are
 2.04e-3 (hip) and 2.02e-3 (torch fp32) at |w| = 32; iteration 1's first-step losses of the two backends
 were equal to the last bit."""
 import ctypes
@@ -37,7 +39,7 @@ def _errors(got, want):
 @pytest.mark.parametrize("k", range(len(R.CASES)), ids=R.IDS)
 def test_parity_with_fp64_autograd(k):
     """e_hip <= 4 e_32 and e_hip < 1e-4, e the largest of the per-tensor rel-L2 of all PISGradNet parameter
-    gradients and the loss's relative error."""
+    gradients and the loss's relative error; and the same factor over the nn_module.* tensors alone."""
     case = R.CASES[k]
     clip = R.make_batch(k)[2]
     want = R.torch_fp64(k)
@@ -47,10 +49,18 @@ def test_parity_with_fp64_autograd(k):
     (g_hip, l_hip), (g_32, l_32) = _errors(hip, want), _errors(t32, want)
     e_hip, e_32 = max(g_hip, l_hip), max(g_32, l_32)
     names = R.param_names(case)
-    worst = max(zip(R.tensor_errors(hip[1], want[1]), names))
+    t_hip, t_32 = R.tensor_errors(hip[1], want[1]), R.tensor_errors(t32[1], want[1])
+    worst = max(zip(t_hip, names))
+    core = [n.startswith("nn_module.") for n in names]  # the tensors the HIP core computes
+    assert any(core) and not all(core)
+    nn_hip, nn_32 = (max(e for e, c in zip(t, core) if c) for t in (t_hip, t_32))
+    time_hip, time_32 = (max(e for e, c in zip(t, core) if not c) for t in (t_hip, t_32))
     print(f"PIS_FIT_PARITY {R.IDS[k]} e_hip {e_hip:.3e} e_32 {e_32:.3e} (grad {g_hip:.3e} / {g_32:.3e}, loss "
-          f"{l_hip:.3e} / {l_32:.3e}; worst hip tensor {worst[1]} {worst[0]:.3e})")
+          f"{l_hip:.3e} / {l_32:.3e}; nn_module {nn_hip:.3e} / {nn_32:.3e}, time networks {time_hip:.3e} / "
+          f"{time_32:.3e}; worst hip tensor {worst[1]} {worst[0]:.3e})")
     assert e_hip <= 4 * e_32 and e_hip < 1e-4, (e_hip, e_32, worst)
+    # the same bound on the core's own tensors: the time networks' larger error does not cover for them
+    assert nn_hip <= 4 * nn_32, (nn_hip, nn_32)
     # the objective's contract: gradient_objective's info keys; the value kind returns {}
     tx, y, _ = R.make_batch(k)
     loss, info = _device_objective(case, clip)(net, tx.to(DEV), y.to(DEV))

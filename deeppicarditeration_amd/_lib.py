@@ -110,6 +110,13 @@ SIGNATURES = {
                                      c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "dpi_fit_core_backward": (c_int, [c_int, c_int, P(c_int), P(c_void_p), P(c_void_p), P(c_void_p), P(c_void_p),
                                       c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "dpi_fit_core_layers_workspace_bytes": (c_size_t, [c_int, c_int, P(c_int), c_int]),
+    "dpi_fit_core_layers_forward": (c_int, [c_int, c_int, P(c_int), P(c_void_p), P(c_void_p), c_void_p, c_int,
+                                            c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t,
+                                            c_void_p]),
+    "dpi_fit_core_layers_backward": (c_int, [c_int, c_int, P(c_int), P(c_void_p), P(c_void_p), P(c_void_p),
+                                             P(c_void_p), c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_size_t,
+                                             c_void_p]),
 }
 
 _lib = None

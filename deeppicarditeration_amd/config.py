@@ -4,7 +4,9 @@ image): the same default schema, `BASE:` chaining with `NAME` joining (config.py
 unchanged.  Keys added by this build: under DATA BACKEND ("hip"), SEED, EULER_STEPS,
 POINTS_PER_CALL; TRAIN.BACKEND ("torch": the fit's objectives in PyTorch-ROCm; "hip": loss and
 parameter gradients in the kernels of csrc/dpi_fit.h); TRAIN.FUSED_STEP (false; true, under TRAIN.BACKEND:
-hip: the Adam / AdamW update of every parameter in the launch that forms its gradient, fit.device_step).
+hip: the Adam / AdamW update of every parameter in the launch that forms its gradient, fit.device_step);
+TRAIN.CORE_FORM ("tiles"; "layers", under TRAIN.BACKEND: hip: a PISGradNet's core as one launch per layer and
+pass over the whole GPU, csrc/dpi_fit_layers.h).
 """
 import ast
 import copy
@@ -121,7 +123,7 @@ def get_default_cfg() -> CfgNode:
     C.TRAIN = _N({"BATCH_SIZE": 2048, "N_EPOCHS": 1, "SUPERVISE_GRADIENT": None, "SUPERVISE_HESSIAN": None,
                   "NUM_HESS_SAMPLES": -1,
                   # this build
-                  "BACKEND": "torch", "FUSED_STEP": False})
+                  "BACKEND": "torch", "FUSED_STEP": False, "CORE_FORM": "tiles"})
     C.TRAIN.LOSS = _N({"beta": 0.0, "use_aux_loss": False, "weight_aux_loss": 0.1})
     C.TRAIN.LOSS.SCALER = _N({"cls": None})
     C.TRAIN.LOSS.SCALER.kwargs = _N(new_allowed=True)
@@ -174,6 +176,20 @@ def check_fused_step(cfg):
                                   "by torch")
 
 
+CORE_FORMS = ("tiles", "layers")
+
+
+def check_core_form(cfg):
+    """TRAIN.CORE_FORM, the form of the PISGradNet core under TRAIN.BACKEND: hip (fit.device_objective), checked
+    when the configuration is loaded; the network is checked at the first batch."""
+    form = cfg.TRAIN.CORE_FORM
+    if form not in CORE_FORMS:
+        raise ValueError(f"TRAIN.CORE_FORM {form!r}: one of {CORE_FORMS}")
+    if form != "tiles" and cfg.TRAIN.BACKEND != "hip":
+        raise NotImplementedError(f"TRAIN.CORE_FORM: {form} with TRAIN.BACKEND: {cfg.TRAIN.BACKEND}: the core's forms "
+                                  "are the HIP fit's (TRAIN.BACKEND: hip)")
+
+
 def _read_file_only(path):
     with open(path) as f:
         return CfgNode(yaml.safe_load(f) or {}, new_allowed=True)
@@ -213,5 +229,6 @@ def load_cfg(cfg_file: str, override: List[str] = None) -> CfgNode:
     if cfg.TRAIN.BACKEND not in ("torch", "hip"):
         raise ValueError(f"TRAIN.BACKEND {cfg.TRAIN.BACKEND!r}: one of 'torch', 'hip'")
     check_fused_step(cfg)
+    check_core_form(cfg)
     cfg.freeze()
     return cfg

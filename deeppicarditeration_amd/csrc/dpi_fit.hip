@@ -1,7 +1,7 @@
 // C ABI of the fit's device path (include/dpi.h: dpi_fit_workspace_bytes, dpi_fit_gradients, dpi_fit_step for
 // construct_mlp value networks; dpi_fit_core_workspace_bytes, dpi_fit_core_forward, dpi_fit_core_backward
-// for PISGradNet's nn_module); the kernels are in dpi_fit.h.  Not a row of the unit table: nothing here
-// depends on a (problem, network) route.
+// for PISGradNet's nn_module, and its layer-wise form dpi_fit_core_layers_*); the kernels are in dpi_fit.h and
+// dpi_fit_layers.h.  Not a row of the unit table: nothing here depends on a (problem, network) route.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -9,6 +9,7 @@
 #include <string>
 
 #include "dpi_fit.h"
+#include "dpi_fit_layers.h"
 #include "dpi_host.h"
 
 namespace {
@@ -103,9 +104,9 @@ size_t core_layout(FitCoreArgs& a) {
   return o;
 }
 
-// what both core entries check and fill: the shape, the parameter tables and the workspace
+// what the core entries of both forms check and fill: the shape, the parameter tables and the workspace
 int core_begin(FitCoreArgs& a, const char* who, int nx, int n_hidden, const int* widths, int B,
-               const float* const* W, const float* const* b, void* ws, size_t ws_bytes) {
+               const float* const* W, const float* const* b, void* ws, size_t ws_bytes, const char* query) {
   const std::string w(who);
   if (!W || !b) return fail(DPI_ERR_ARG, w + ": null pointer table (W, b)");
   for (int l = 0; l <= n_hidden; ++l)
@@ -115,7 +116,7 @@ int core_begin(FitCoreArgs& a, const char* who, int nx, int n_hidden, const int*
   if ((uintptr_t)ws % 4) return fail(DPI_ERR_ARG, w + ": the workspace must be 4-byte aligned");
   if (!ws || ws_bytes < need)
     return fail(DPI_ERR_WORKSPACE, w + ": workspace too small (" + std::to_string(ws_bytes) + " < " +
-                                   std::to_string(need) + " bytes, dpi_fit_core_workspace_bytes)");
+                                   std::to_string(need) + " bytes, " + query + ")");
   for (int l = 0; l <= n_hidden; ++l) {
     a.W[l] = W[l];
     a.b[l] = b[l];
@@ -133,18 +134,24 @@ extern "C" size_t dpi_fit_core_workspace_bytes(int nx, int n_hidden, const int* 
   return core_layout(a) * sizeof(float);
 }
 
-extern "C" int dpi_fit_core_forward(int nx, int n_hidden, const int* widths, const float* const* W,
-                                    const float* const* b, const float* tau, int tau_stride, const float* x,
-                                    int x_stride, int B, float* sp, float* q, void* ws, size_t ws_bytes,
-                                    void* stream) {
+namespace {
+
+// the workspace query a "workspace too small" text names, by form
+constexpr const char* TILES_QUERY = "dpi_fit_core_workspace_bytes";
+constexpr const char* LAYERS_QUERY = "dpi_fit_core_layers_workspace_bytes";
+
+// the forward entry of either form as `who`: 0 with `a` ready to launch, 1 for an empty batch, or the code with
+// the text set
+int core_forward_begin(FitCoreArgs& a, const std::string& who, const char* query, int nx, int n_hidden,
+                       const int* widths, const float* const* W, const float* const* b, const float* tau,
+                       int tau_stride, const float* x, int x_stride, int B, float* sp, float* q, void* ws,
+                       size_t ws_bytes) {
   int rc = core_shape(nx, n_hidden, widths, B);
   if (rc) return rc;
-  if (tau_stride < CORE_NT || x_stride < nx)
-    return fail(DPI_ERR_ARG, "fit_core_forward: row stride of tau < 64 or of x < nx");
-  if (B == 0) return 0;
-  if (!tau || !x || !sp) return fail(DPI_ERR_ARG, "fit_core_forward: null tau, x or sp");
-  FitCoreArgs a{};
-  rc = core_begin(a, "fit_core_forward", nx, n_hidden, widths, B, W, b, ws, ws_bytes);
+  if (tau_stride < CORE_NT || x_stride < nx) return fail(DPI_ERR_ARG, who + ": row stride of tau < 64 or of x < nx");
+  if (B == 0) return 1;
+  if (!tau || !x || !sp) return fail(DPI_ERR_ARG, who + ": null tau, x or sp");
+  rc = core_begin(a, who.c_str(), nx, n_hidden, widths, B, W, b, ws, ws_bytes, query);
   if (rc) return rc;
   a.tau = tau;
   a.x = x;
@@ -153,24 +160,22 @@ extern "C" int dpi_fit_core_forward(int nx, int n_hidden, const int* widths, con
   a.sp = sp;
   a.q = q;
   a.grad = q ? 1 : 0;
-  hipLaunchKernelGGL(k_fit_core_fwd, dim3(a.tiles), dim3(FIT_NTH), 0, (hipStream_t)stream, a);
-  HIPCHK(hipGetLastError());
   return 0;
 }
 
-extern "C" int dpi_fit_core_backward(int nx, int n_hidden, const int* widths, const float* const* W,
-                                     const float* const* b, float* const* dW, float* const* db, const float* e,
-                                     const float* r, int B, float* dtau, void* ws, size_t ws_bytes, void* stream) {
+// the backward entry of either form, as core_forward_begin; blk: k_fit_core_wgrad's workgroups
+int core_backward_begin(FitCoreArgs& a, int& blk, const std::string& who, const char* query, int nx, int n_hidden,
+                        const int* widths, const float* const* W, const float* const* b, float* const* dW,
+                        float* const* db, const float* e, const float* r, int B, float* dtau, void* ws,
+                        size_t ws_bytes) {
   int rc = core_shape(nx, n_hidden, widths, B);
   if (rc) return rc;
-  if (B == 0) return 0;
-  if (!dW || !db) return fail(DPI_ERR_ARG, "fit_core_backward: null pointer table (dW, db)");
+  if (B == 0) return 1;
+  if (!dW || !db) return fail(DPI_ERR_ARG, who + ": null pointer table (dW, db)");
   for (int l = 0; l <= n_hidden; ++l)
-    if (!dW[l] || !db[l])
-      return fail(DPI_ERR_ARG, "fit_core_backward: null entry in a gradient table at layer " + std::to_string(l));
-  if (!e || !dtau) return fail(DPI_ERR_ARG, "fit_core_backward: null e or dtau");
-  FitCoreArgs a{};
-  rc = core_begin(a, "fit_core_backward", nx, n_hidden, widths, B, W, b, ws, ws_bytes);
+    if (!dW[l] || !db[l]) return fail(DPI_ERR_ARG, who + ": null entry in a gradient table at layer " + std::to_string(l));
+  if (!e || !dtau) return fail(DPI_ERR_ARG, who + ": null e or dtau");
+  rc = core_begin(a, who.c_str(), nx, n_hidden, widths, B, W, b, ws, ws_bytes, query);
   if (rc) return rc;
   for (int l = 0; l <= n_hidden; ++l) {
     a.dW[l] = dW[l];
@@ -180,12 +185,97 @@ extern "C" int dpi_fit_core_backward(int nx, int n_hidden, const int* widths, co
   a.r = r;
   a.grad = r ? 1 : 0;
   a.dtau = dtau;
-  int blk = 0;
+  blk = 0;
   for (int l = 1; l <= n_hidden + 1; ++l) {
     a.blk0[l - 1] = blk;
     blk += ((a.n[l] + FIT_WT - 1) / FIT_WT) * ((a.n[l - 1] + FIT_WT - 1) / FIT_WT);
   }
   a.blk0[n_hidden + 1] = blk;
+  return 0;
+}
+
+// one launch of the layer-wise form: layer l of `a`, `units` output units from the epilogue's first
+template <int ORI, int EPI>
+int launch_layer(const FitCoreArgs& a, int l, int units, hipStream_t st) {
+  hipLaunchKernelGGL((k_fit_layer<ORI, EPI>), dim3(a.tiles, (units + LAY_UT - 1) / LAY_UT), dim3(LAY_NTH), 0, st, a, l);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+}  // namespace
+
+extern "C" size_t dpi_fit_core_layers_workspace_bytes(int nx, int n_hidden, const int* widths, int B) {
+  return dpi_fit_core_workspace_bytes(nx, n_hidden, widths, B);  // the same arrays, no region of its own
+}
+
+extern "C" int dpi_fit_core_layers_forward(int nx, int n_hidden, const int* widths, const float* const* W,
+                                           const float* const* b, const float* tau, int tau_stride, const float* x,
+                                           int x_stride, int B, float* sp, float* q, void* ws, size_t ws_bytes,
+                                           void* stream) {
+  FitCoreArgs a{};
+  int rc = core_forward_begin(a, "fit_core_layers_forward", LAYERS_QUERY, nx, n_hidden, widths, W, b, tau, tau_stride,
+                              x, x_stride, B, sp, q, ws, ws_bytes);
+  if (rc) return rc < 0 ? rc : 0;
+  hipStream_t st = (hipStream_t)stream;
+  const int L = n_hidden;
+  hipLaunchKernelGGL(k_fit_layers_a0, dim3(a.tiles, (a.n[0] + LAY_UT - 1) / LAY_UT), dim3(LAY_NTH), 0, st, a);
+  HIPCHK(hipGetLastError());
+  for (int l = 1; l <= L; ++l)  // 1. forward
+    if ((rc = launch_layer<LAY_N, LAY_ACT>(a, l, a.n[l], st))) return rc;
+  if ((rc = launch_layer<LAY_N, LAY_OUT>(a, L + 1, nx, st))) return rc;
+  hipLaunchKernelGGL(k_fit_layers_sp, dim3(a.tiles), dim3(FIT_ROWS), 0, st, a);
+  HIPCHK(hipGetLastError());
+  if (!a.grad) return 0;
+  for (int l = L + 1; l >= 2; --l)  // 2. adjoint
+    if ((rc = launch_layer<LAY_T, LAY_ADJ>(a, l, a.n[l - 1], st))) return rc;
+  return launch_layer<LAY_T, LAY_Q>(a, 1, nx, st);
+}
+
+extern "C" int dpi_fit_core_layers_backward(int nx, int n_hidden, const int* widths, const float* const* W,
+                                            const float* const* b, float* const* dW, float* const* db,
+                                            const float* e, const float* r, int B, float* dtau, void* ws,
+                                            size_t ws_bytes, void* stream) {
+  FitCoreArgs a{};
+  int blk = 0;
+  int rc = core_backward_begin(a, blk, "fit_core_layers_backward", LAYERS_QUERY, nx, n_hidden, widths, W, b, dW, db,
+                               e, r, B, dtau, ws, ws_bytes);
+  if (rc) return rc < 0 ? rc : 0;
+  hipStream_t st = (hipStream_t)stream;
+  const int L = n_hidden;
+  hipLaunchKernelGGL(k_fit_layers_seed, dim3(a.tiles, (a.n[0] + LAY_UT - 1) / LAY_UT), dim3(LAY_NTH), 0, st, a);
+  HIPCHK(hipGetLastError());
+  if (a.grad)
+    for (int l = 1; l <= L; ++l)  // 3. tangent
+      if ((rc = launch_layer<LAY_N, LAY_TAN>(a, l, a.n[l], st))) return rc;
+  for (int l = L + 1; l >= 2; --l)  // 4. reverse
+    if ((rc = launch_layer<LAY_T, LAY_REV>(a, l, a.n[l - 1], st))) return rc;
+  if ((rc = launch_layer<LAY_T, LAY_DTAU>(a, 1, CORE_NT, st))) return rc;
+  hipLaunchKernelGGL(k_fit_core_wgrad, dim3(blk), dim3(256), 0, st, a);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+extern "C" int dpi_fit_core_forward(int nx, int n_hidden, const int* widths, const float* const* W,
+                                    const float* const* b, const float* tau, int tau_stride, const float* x,
+                                    int x_stride, int B, float* sp, float* q, void* ws, size_t ws_bytes,
+                                    void* stream) {
+  FitCoreArgs a{};
+  const int rc = core_forward_begin(a, "fit_core_forward", TILES_QUERY, nx, n_hidden, widths, W, b, tau, tau_stride,
+                                    x, x_stride, B, sp, q, ws, ws_bytes);
+  if (rc) return rc < 0 ? rc : 0;
+  hipLaunchKernelGGL(k_fit_core_fwd, dim3(a.tiles), dim3(FIT_NTH), 0, (hipStream_t)stream, a);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+extern "C" int dpi_fit_core_backward(int nx, int n_hidden, const int* widths, const float* const* W,
+                                     const float* const* b, float* const* dW, float* const* db, const float* e,
+                                     const float* r, int B, float* dtau, void* ws, size_t ws_bytes, void* stream) {
+  FitCoreArgs a{};
+  int blk = 0;
+  const int rc = core_backward_begin(a, blk, "fit_core_backward", TILES_QUERY, nx, n_hidden, widths, W, b, dW, db, e,
+                                     r, B, dtau, ws, ws_bytes);
+  if (rc) return rc < 0 ? rc : 0;
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(k_fit_core_bwd, dim3(a.tiles), dim3(FIT_NTH), 0, st, a);
   HIPCHK(hipGetLastError());

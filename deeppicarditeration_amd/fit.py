@@ -3,7 +3,8 @@
 loss and the parameter gradients of the value and gradient kinds come from the HIP kernels of
 csrc/dpi_fit.h (`device_objective`, DESIGN.md §5.1): in two launches for a construct_mlp value network;
 for a PISGradNet, nn_module and its double backward in three launches (`_PISCore`) between the time networks
-and the loss, which stay torch's.  The fit consumes the device-resident labels.
+and the loss, which stay torch's — or, under TRAIN.CORE_FORM: layers, in one launch per layer and pass
+(csrc/dpi_fit_layers.h).  The fit consumes the device-resident labels.
 
 - `value_objective`: PicardBaseSolution.training_step (picard/solution.py:74-81), the exp(beta t)
   weighted value loss;
@@ -322,17 +323,32 @@ class _DeviceFit(torch.autograd.Function):
 
 
 PIS_CHANNELS, PIS_LAYERS_MAX, PIS_WIDTH_MAX, PIS_NX_MAX = 64, 4, 512, 128  # csrc/dpi_fit.h CORE_*
+# TRAIN.CORE_FORM -> the C entries of the PISGradNet core (workspace bytes, forward, backward): "tiles" is one
+# workgroup per 64 rows through all layers (csrc/dpi_fit.h), "layers" one launch per layer and pass over
+# (row tile x unit block) (csrc/dpi_fit_layers.h).  Same primitive, contract and workspace arrays.
+CORE_FORMS = {"tiles": ("dpi_fit_core_workspace_bytes", "dpi_fit_core_forward", "dpi_fit_core_backward"),
+              "layers": ("dpi_fit_core_layers_workspace_bytes", "dpi_fit_core_layers_forward",
+                         "dpi_fit_core_layers_backward")}
+
+
+def _check_core_form(core_form):
+    if core_form not in CORE_FORMS:
+        raise ValueError(f"TRAIN.CORE_FORM {core_form!r}: one of {tuple(CORE_FORMS)}")
 
 
 class _PISPlan:
     """What `device_objective` needs of one PISGradNet (this build's class or the reference's of that
     name), checked once and before the library is touched: the closed-form g and g_x behind g0, the
     Linear layers of `nn_module` (the part the HIP core computes), its parameters in state-dict order
-    and the C-ABI shape arguments.  What the core does not cover is refused by name."""
+    and the C-ABI shape arguments.  What the core does not cover is refused by name.  core_form
+    (TRAIN.CORE_FORM) names the C entries `_PISCore` calls."""
 
-    def __init__(self, net, nx):
+    def __init__(self, net, nx, core_form="tiles"):
         from . import _lib
+        _check_core_form(core_form)
         self.net = net
+        self.core_form = core_form
+        self.ws_bytes, self.forward, self.backward = CORE_FORMS[core_form]
         owner = getattr(net.g0, "__self__", None)
         if owner is None or type(owner).__name__ != "OUProcessEquation":
             raise NotImplementedError("TRAIN.BACKEND: hip with a PISGradNet whose g0 is not the bound method g of an "
@@ -378,7 +394,8 @@ class _PISCore(torch.autograd.Function):
     """PISGradNet's nn_module N as one differentiable primitive: (tau (B, 64), x (B, nx),
     *params) -> sp = x . N(tau, x) (B, 1) and q = d sp / d x (B, nx), from dpi_fit_core_forward; backward
     is dpi_fit_core_backward (the gradients of tau and of the parameters; x is data and gets none), so
-    no torch double backward is involved.  grad False: only sp is formed, q is empty."""
+    no torch double backward is involved.  grad False: only sp is formed, q is empty.  Under
+    TRAIN.CORE_FORM: layers the plan names dpi_fit_core_layers_forward / _backward instead."""
 
     @staticmethod
     def forward(ctx, plan, grad, tau, x, *params):
@@ -390,16 +407,16 @@ class _PISCore(torch.autograd.Function):
         if x.stride(-1) != 1:
             x = x.contiguous()
         B, nx = int(x.shape[0]), plan.nx
-        need = int(lib.dpi_fit_core_workspace_bytes(nx, plan.n_hidden, plan.widths, B))
+        need = int(getattr(lib, plan.ws_bytes)(nx, plan.n_hidden, plan.widths, B))
         if plan.ws is None or plan.ws.numel() < need or plan.ws.device != x.device:
             plan.ws = torch.empty(max(need, 4), dtype=torch.uint8, device=x.device)
         sp = torch.empty(B, 1, dtype=torch.float32, device=x.device)
         q = torch.empty(B if grad else 0, nx, dtype=torch.float32, device=x.device)
-        _lib.check(lib.dpi_fit_core_forward(nx, plan.n_hidden, plan.widths, plan.table(params[0::2]),
-                                            plan.table(params[1::2]), tau.data_ptr(), int(tau.stride(0)), x.data_ptr(),
-                                            int(x.stride(0)), B, sp.data_ptr(), q.data_ptr() if grad else None,
-                                            plan.ws.data_ptr(), plan.ws.numel(),
-                                            torch.cuda.current_stream(x.device).cuda_stream), "dpi_fit_core_forward")
+        _lib.check(getattr(lib, plan.forward)(nx, plan.n_hidden, plan.widths, plan.table(params[0::2]),
+                                              plan.table(params[1::2]), tau.data_ptr(), int(tau.stride(0)),
+                                              x.data_ptr(), int(x.stride(0)), B, sp.data_ptr(),
+                                              q.data_ptr() if grad else None, plan.ws.data_ptr(), plan.ws.numel(),
+                                              torch.cuda.current_stream(x.device).cuda_stream), plan.forward)
         plan.calls += 1
         ctx.plan, ctx.grad, ctx.call, ctx.params, ctx.B = plan, grad, plan.calls, params, B
         if not grad:
@@ -419,11 +436,12 @@ class _PISCore(torch.autograd.Function):
         r = g_q.float().contiguous() if ctx.grad and g_q is not None else None
         grads = [torch.empty_like(p) for p in params]
         dtau = torch.empty(B, PIS_CHANNELS, dtype=torch.float32, device=dev)
-        _lib.check(lib.dpi_fit_core_backward(plan.nx, plan.n_hidden, plan.widths, plan.table(params[0::2]),
-                                             plan.table(params[1::2]), plan.table(grads[0::2]),
-                                             plan.table(grads[1::2]), e.data_ptr(), None if r is None else r.data_ptr(),
-                                             B, dtau.data_ptr(), plan.ws.data_ptr(), plan.ws.numel(),
-                                             torch.cuda.current_stream(dev).cuda_stream), "dpi_fit_core_backward")
+        _lib.check(getattr(lib, plan.backward)(plan.nx, plan.n_hidden, plan.widths, plan.table(params[0::2]),
+                                               plan.table(params[1::2]), plan.table(grads[0::2]),
+                                               plan.table(grads[1::2]), e.data_ptr(),
+                                               None if r is None else r.data_ptr(), B, dtau.data_ptr(),
+                                               plan.ws.data_ptr(), plan.ws.numel(),
+                                               torch.cuda.current_stream(dev).cuda_stream), plan.backward)
         return (None, None, dtau, None) + tuple(grads)
 
 
@@ -477,20 +495,29 @@ def _device_loss_args(loss_fn, scaler):
     return loss_kind, clip, c, c <= 1e-9
 
 
-def device_objective(beta, loss_fn, scaler, nx):
+def device_objective(beta, loss_fn, scaler, nx, core_form="tiles"):
     """The device form of `value_objective` (scaler None, or a FixedLossScaler of weight <= 1e-9) and of
     `gradient_objective` with a FixedLossScaler: loss and parameter gradients from the HIP kernels of
     csrc/dpi_fit.h, same signature and `info` keys.  The optimizer stays torch's:
     `loss.sum().backward()` delivers the gradients the forward launch computed.  The network decides at
     the first batch: a construct_mlp value network takes `_DeviceFit` (loss and gradients in two launches),
-    a PISGradNet takes `_pis_objective` (nn_module in HIP through `_PISCore`, the rest in torch)."""
+    a PISGradNet takes `_pis_objective` (nn_module in HIP through `_PISCore`, the rest in torch).
+    core_form (TRAIN.CORE_FORM): the form of the PISGradNet core, "tiles" or "layers"; "layers" with any other
+    network is refused by name at the first batch, before the library is touched."""
+    _check_core_form(core_form)
     loss_kind, clip, c, value_only = _device_loss_args(loss_fn, scaler)
     plans = {}
 
     def objective(net, tx, y):
         plan = plans.get(id(net))
         if plan is None or plan.net is not net:
-            plan = plans[id(net)] = (_PISPlan if type(net).__name__ == "PISGradNet" else _DevicePlan)(net, nx)
+            if type(net).__name__ == "PISGradNet":
+                plan = plans[id(net)] = _PISPlan(net, nx, core_form)
+            elif core_form != "tiles":
+                raise NotImplementedError(f"TRAIN.CORE_FORM: {core_form} with a {type(net).__name__} network: the "
+                                          "forms are the PISGradNet core's (NETWORK.PISGRADNET)")
+            else:
+                plan = plans[id(net)] = _DevicePlan(net, nx)
         if isinstance(plan, _PISPlan):
             return _pis_objective(plan, tx, y, beta, loss_fn, scaler, value_only)
         total, parts = _DeviceFit.apply(plan, tx, y, beta, loss_kind, clip, 0.0 if value_only else c, *plan.params)
@@ -548,7 +575,7 @@ def _fused_state(opt, plan):
     return states
 
 
-def device_step(beta, loss_fn, scaler, nx):
+def device_step(beta, loss_fn, scaler, nx, core_form="tiles"):
     """One whole training step on the device (TRAIN.FUSED_STEP under TRAIN.BACKEND: hip):
     `step(net, opt, tx, y) -> losses (2 + nx,)` = (total, v_loss, g_loss[nx]) of the batch, formed before the
     update, from dpi_fit_step: k_fit_rows and k_fit_wgrad_step compute the loss and the gradients and apply
@@ -558,13 +585,18 @@ def device_step(beta, loss_fn, scaler, nx):
     working), the moments and the counter live in `opt.state` in torch's layout (so `opt.state_dict()` is
     torch's and a run may switch between the two step forms).  Same options as `device_objective`; an
     optimizer or network the kernel does not cover is refused by name at the first batch, before the library
-    is touched.  There is no fallback."""
+    is touched.  There is no fallback.  core_form other than "tiles" is refused as `device_objective` refuses
+    it: the fused step has no PISGradNet core."""
+    _check_core_form(core_form)
     loss_kind, clip, c, value_only = _device_loss_args(loss_fn, scaler)
     plans = {}
 
     def step(net, opt, tx, y):
         plan = plans.get(id(net))
         if plan is None or plan.net is not net:
+            if core_form != "tiles" and type(net).__name__ != "PISGradNet":
+                raise NotImplementedError(f"TRAIN.CORE_FORM: {core_form} with a {type(net).__name__} network: the "
+                                          "forms are the PISGradNet core's (NETWORK.PISGRADNET)")
             if type(net).__name__ == "PISGradNet":
                 raise NotImplementedError("TRAIN.FUSED_STEP with NETWORK.PISGRADNET (a PISGradNet): its time networks "
                                           "are fitted by torch")
@@ -606,7 +638,7 @@ def make_scaler(scaler_cfg):
 
 
 def build_objective(train_cfg, nx, supervise_gradient, supervise_hessian, output_dim=1, backend="torch",
-                    fused_step=False):
+                    fused_step=False, core_form="tiles"):
     """PicardRunner.get_solution (picard_iteration.py:113-118) + the wrappers' construct_solution
     (solution_jac.py:112-119): returns (objective, kind) with kind in {"value", "gradient",
     "gradient_hessian", "head_value_gradient", "head_only_gradient"}.  output_dim: the network's
@@ -615,15 +647,20 @@ def build_objective(train_cfg, nx, supervise_gradient, supervise_hessian, output
     backend (TRAIN.BACKEND): "torch" builds the objectives above; "hip" builds `device_objective` for the
     kinds "value" and "gradient" with FixedLossScaler and refuses every other option by name.
     fused_step (TRAIN.FUSED_STEP, "hip" only): what is returned in the objective's place is the `device_step`
-    of the same options, for `fused_train_steps`."""
+    of the same options, for `fused_train_steps`.
+    core_form (TRAIN.CORE_FORM, other than "tiles" under "hip" only): handed to `device_objective`."""
     if backend not in BACKENDS:
         raise ValueError(f"TRAIN.BACKEND {backend!r}: one of {BACKENDS}")
+    _check_core_form(core_form)
+    if core_form != "tiles" and backend != "hip":
+        raise NotImplementedError(f"TRAIN.CORE_FORM: {core_form} with TRAIN.BACKEND: {backend}: the core's forms are "
+                                  "the HIP fit's (TRAIN.BACKEND: hip)")
     if fused_step and backend != "hip":
         raise NotImplementedError(f"TRAIN.FUSED_STEP with TRAIN.BACKEND: {backend}: the fused step is the HIP fit's "
                                   "(TRAIN.BACKEND: hip)")
     if backend == "hip":
         return _build_device_objective(train_cfg, nx, supervise_gradient, supervise_hessian, output_dim,
-                                       device_step if fused_step else device_objective)
+                                       device_step if fused_step else device_objective, core_form)
     loss_cfg = train_cfg["LOSS"]
     beta = float(loss_cfg["beta"])
     loss_fn = make_loss_fn(loss_cfg.get("FN"))
@@ -661,10 +698,12 @@ def build_objective(train_cfg, nx, supervise_gradient, supervise_hessian, output
     return gradient_objective(beta, loss_fn, scaler, nx), "gradient"
 
 
-def _build_device_objective(train_cfg, nx, supervise_gradient, supervise_hessian, output_dim, make):
+def _build_device_objective(train_cfg, nx, supervise_gradient, supervise_hessian, output_dim, make,
+                            core_form="tiles"):
     """build_objective under TRAIN.BACKEND: hip.  The options the fit kernels do not cover raise
     NotImplementedError naming the option; the network itself is checked at the first batch.
     make: `device_objective`, or `device_step` under TRAIN.FUSED_STEP."""
+    form = {} if core_form == "tiles" else {"core_form": core_form}  # the default reproduces the calls as they were
     loss_cfg = train_cfg["LOSS"]
     beta = float(loss_cfg["beta"])
     loss_fn = make_loss_fn(loss_cfg.get("FN"))
@@ -675,7 +714,7 @@ def _build_device_objective(train_cfg, nx, supervise_gradient, supervise_hessian
         raise NotImplementedError("TRAIN.BACKEND: hip with TRAIN.SUPERVISE_HESSIAN: the fit kernels have the value "
                                   "and gradient losses only")
     if not supervise_gradient:
-        return make(beta, loss_fn, None, nx), "value"
+        return make(beta, loss_fn, None, nx, **form), "value"
     if bool(loss_cfg.get("use_aux_loss")):
         raise NotImplementedError("TRAIN.LOSS.use_aux_loss applies to ValueGradient networks only")
     scaler = make_scaler(loss_cfg.get("SCALER"))
@@ -683,7 +722,7 @@ def _build_device_objective(train_cfg, nx, supervise_gradient, supervise_hessian
         raise NotImplementedError(f"TRAIN.BACKEND: hip with TRAIN.LOSS.SCALER {type(scaler).__name__}: "
                                   "FixedLossScaler only")
     kind = "value" if scaler.fixed_weight <= 1e-9 else "gradient"
-    return make(beta, loss_fn, scaler, nx), kind
+    return make(beta, loss_fn, scaler, nx, **form), kind
 
 
 def make_optimizer(params, opt_cfg):

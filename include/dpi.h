@@ -35,6 +35,9 @@
  *   dpi_set_gemm_precision   (no reference counterpart: MFMA precision of the network evaluation)
  *   dpi_fit_gradients        picard/solution.py:74-81, picard/solution_jac.py:167-213  training_step + its backward
  *   dpi_fit_step             the same + picard/solution.py:94-126  the torch.optim.Adam / AdamW step after it
+ *   dpi_fit_core_layers_forward / dpi_fit_core_layers_backward  picard/solution.py:138-289  PISGradNet's nn_module
+ *                            and its double backward as dpi_fit_core_forward / _backward compute them, one launch
+ *                            per layer and pass (dpi_fit_core_layers_workspace_bytes: their workspace)
  */
 #ifndef DPI_H_
 #define DPI_H_
@@ -486,6 +489,23 @@ int dpi_fit_core_forward(int nx, int n_hidden, const int* widths, const float* c
 int dpi_fit_core_backward(int nx, int n_hidden, const int* widths, const float* const* W, const float* const* b,
                           float* const* dW, float* const* db, const float* e, const float* r, int B,
                           float* dtau, void* ws, size_t ws_bytes, void* stream);
+
+/* --- the layer-wise form of the same primitive (additions within ABI 8).  Same arguments, contract, caps,
+ * checks, error codes and exactness class as dpi_fit_core_*: exact fp32 (v_mfma_f32_16x16x4_f32, a k-ordered
+ * fmaf chain), every sum in a fixed order, bitwise reproducible; not the same bits as dpi_fit_core_*, whose
+ * sums take their terms in another order.  One launch per layer and pass over (64-row tile x 16 output
+ * units) instead of one workgroup per 64 rows through all layers: 2 n_hidden + 4 launches (forward with q;
+ * n_hidden + 3 without) and 2 n_hidden + 3 (backward with r; n_hidden + 3 without), all on `stream`, no
+ * atomics and no host synchronisation.  A forward call of one form pairs with the backward call of the same
+ * form.  ws: >= dpi_fit_core_layers_workspace_bytes(nx, n_hidden, widths, B) bytes, which is not below
+ * dpi_fit_core_workspace_bytes of the same shape. */
+size_t dpi_fit_core_layers_workspace_bytes(int nx, int n_hidden, const int* widths, int B);
+int dpi_fit_core_layers_forward(int nx, int n_hidden, const int* widths, const float* const* W,
+                                const float* const* b, const float* tau, int tau_stride, const float* x,
+                                int x_stride, int B, float* sp, float* q, void* ws, size_t ws_bytes, void* stream);
+int dpi_fit_core_layers_backward(int nx, int n_hidden, const int* widths, const float* const* W,
+                                 const float* const* b, float* const* dW, float* const* db, const float* e,
+                                 const float* r, int B, float* dtau, void* ws, size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -16,6 +16,10 @@ device run below every torch run, and the gain against 3 x the spread of the tor
 construct_mlp shapes: "fused" (TRAIN.FUSED_STEP: fit.device_step, loss, gradients and the Adam update in
 dpi_fit_step's two launches) against "unfused" (the device objective, backward and torch's Adam), the
 baseline; --form fused|unfused runs that one form alone once per shape (for a kernel trace).
+
+--core-form tiles|layers (TRAIN.CORE_FORM) times, for the two PISGradNet shapes, the device objective with that
+form of the core against torch; with --against-tiles, "layers" against "tiles" instead, alternating in the
+same way; with --form-alone, that form alone once per shape (for a kernel trace).
 """
 import argparse
 import json
@@ -48,8 +52,9 @@ def time_steps(name, backend, B, nx, widths, c, reps, warmup):
     net = make_net(name, nx, widths).to("cuda")
     scaler = fit.FixedLossScaler(c)
     make = {"hip": fit.device_objective, "unfused": fit.device_objective, "fused": fit.device_step,
-            "torch": fit.gradient_objective}[backend]
-    objective = make(0.0, torch.square, scaler, nx)
+            "torch": fit.gradient_objective, "tiles": fit.device_objective, "layers": fit.device_objective}[backend]
+    form = {"core_form": backend} if backend in ("tiles", "layers") else {}
+    objective = make(0.0, torch.square, scaler, nx, **form)
     steps = fit.fused_train_steps if backend == "fused" else fit.train_steps
     opt = torch.optim.Adam(net.parameters(), lr=1e-3)
     tx = torch.cat([torch.rand(B, 1), torch.randn(B, nx)], 1).to("cuda")
@@ -79,14 +84,26 @@ def main():
     ap.add_argument("--only", default="", help="time the shapes whose name contains this")
     ap.add_argument("--step-forms", action="store_true", help="time the fused step against the unfused hip step")
     ap.add_argument("--form", choices=("fused", "unfused"), default=None, help="run this step form alone, once")
+    ap.add_argument("--core-form", choices=("tiles", "layers"), default=None,
+                    help="the PISGradNet shapes with this form of the core (TRAIN.CORE_FORM) against torch")
+    ap.add_argument("--against-tiles", action="store_true", help="with --core-form layers: against tiles, not torch")
+    ap.add_argument("--form-alone", action="store_true", help="with --core-form: run that form alone, once")
     a = ap.parse_args()
     assert a.reps >= 20, "the median of at least 20 steps"
     forms = a.step_forms or a.form is not None
+    core = a.core_form is not None
+    assert not (core and forms), "--core-form is for the PISGradNet shapes, --step-forms / --form for the others"
+    assert core or not (a.against_tiles or a.form_alone), "--against-tiles and --form-alone go with --core-form"
+    assert not a.against_tiles or a.core_form == "layers", "--against-tiles compares layers with tiles"
     new, old = ("fused", "unfused") if forms else ("hip", "torch")
-    for name, B, nx, widths, c in [s for s in SHAPES if a.only in s[0] and not (forms and "pisgradnet" in s[0])]:
-        if a.form is not None:
-            r = time_steps(name, a.form, B, nx, widths, c, a.reps, a.warmup)
-            print(json.dumps({"shape": name, "backend": a.form, **r}), flush=True)
+    if core:
+        new, old = a.core_form, "tiles" if a.against_tiles else "torch"
+    alone = a.form if a.form is not None else (a.core_form if a.form_alone else None)
+    for name, B, nx, widths, c in [s for s in SHAPES if a.only in s[0] and not (forms and "pisgradnet" in s[0])
+                                   and not (core and "pisgradnet" not in s[0])]:
+        if alone is not None:
+            r = time_steps(name, alone, B, nx, widths, c, a.reps, a.warmup)
+            print(json.dumps({"shape": name, "backend": alone, **r}), flush=True)
             continue
         runs = {new: [], old: []}
         for _ in range(a.pairs):

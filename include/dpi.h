@@ -300,7 +300,13 @@ int dpi_point_baseline(dpi_problem p, dpi_net net, const float* tx, int n, void*
  * 64) workgroups per point; the lanes of the last one with m >= m_end roll out like any other and
  * contribute exactly +0 to every sum, so the block tree, dpi_moments_reduce and the 1 / M of the
  * finalize calls are those of whole blocks (M = 1 costs what M = 64 costs).  moments (n, 2, 1+nx) fp32: [0] = sum of per-path
- * contributions, [1] = sum of squares.  Summation order is fixed (pairwise over 64-path
+ * contributions, [1] = sum of squares, each square formed per path before any sum (the value column's
+ * of c_T + c_I + f_b (T - t), live lanes only).  Both halves are tested entry by entry against the fp64
+ * oracle (tests/test_gpu_moments.py: |sum - ref| / sqrt(M sum c^2) and |sum c^2 - ref| / ref below 1e-4
+ * for every point and column, through every entry point that returns moments: this call, its
+ * finalizing, prepared and ranged forms, dpi_generate_with_gradients, dpi_sample_with_gradients,
+ * dpi_moments_reduce and dpi_label_moments_hessians, whose Hessian sums are held to the same bar).
+ * Summation order is fixed (pairwise over 64-path
  * blocks), so results are bit-reproducible; ranges aligned to power-of-two block counts
  * combine with dpi_moments_reduce bit-identically to a single call.  Requires
  * dpi_point_baseline (or dpi_sample_points_baseline) of the same n points on the same workspace

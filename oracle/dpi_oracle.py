@@ -517,17 +517,21 @@ def rel_l2_parts(a, b):
 
 
 # ----------------------------------------------------------------------------- moments (sharding)
-def path_contributions(eq, net, tx_row, ig, m, K, seed, epoch=0, delta_t=0.0, flags=3):
+def path_contributions(eq, net, tx_row, ig, m, K, seed, epoch=0, delta_t=0.0, flags=3, v=0, return_baseline=False):
     """Per-path contribution rows c (len(m), 1+nx) whose mean (+ g(x) in column 0) is the label
     (picard/data.py:923-925, :523-526; TD :947-951, :570-574), for one point and MC indices m.
-    flags (DPI_TERMINAL = 1 | DPI_INTEGRAL = 2): the estimators included."""
+    flags (DPI_TERMINAL = 1 | DPI_INTEGRAL = 2): the estimators included.  v > 0: SDGD (GBM) with the
+    per-path indices and the per-path baseline f_b of labels_grad.  return_baseline: also the baseline
+    term f_b * horizon of every path (len(m),), the part of c[:, 0] that does not depend on the path's
+    noise (zero without the integral estimator)."""
     t = float(tx_row[0])
     x = np.asarray(tx_row[1:], np.float64)[None]
     a = eq.alpha_sqrt
     hmt, td_u = td_horizon(eq, t, delta_t)
     g_x = eq.g(x)[0, 0]
-    fb = _f_and_extras(eq, net, np.array([[t]]), x)[0][0, 0]
-    S_T, S_s, U, _ = path_noise(eq, ig, np.asarray(m), K, seed, epoch)
+    m = np.asarray(m)
+    S_T, S_s, U, idx = path_noise(eq, ig, m, K, seed, epoch, v)
+    sdgd = idx is not None and eq.has_hessian_term
     W_T = math.sqrt(hmt / K) * S_T
     Y = W_T / hmt / a
     if td_u:
@@ -536,7 +540,14 @@ def path_contributions(eq, net, tx_row, ig, m, K, seed, epoch=0, delta_t=0.0, fl
         cT = eq.g(x + a * W_T) - g_x
     s = (U * hmt + t)[:, None]
     W_s = np.sqrt((s - t) / K) * S_s
-    f, _ = _f_and_extras(eq, net, s, x + a * W_s)
+    if sdgd:  # labels_grad: u_ii at the path's indices, the baseline's from the point's Hessian diagonal
+        hd_b = net.value_grad(np.concatenate([[[t]], x], -1), need_hdiag=True)[2]
+        f, _ = _f_and_extras(eq, net, s, x + a * W_s, sdgd_idx=idx)
+        fb, _ = _f_and_extras(eq, net, np.full((len(m), 1), t), np.repeat(x, len(m), 0), sdgd_idx=idx,
+                              base_hdiag=np.repeat(hd_b, len(m), 0))
+    else:
+        fb = _f_and_extras(eq, net, np.array([[t]]), x)[0][0, 0]
+        f, _ = _f_and_extras(eq, net, s, x + a * W_s)
     cI = hmt * (f - fb)
     Ys = W_s / (s - t) / a
     if not flags & 1:
@@ -544,13 +555,16 @@ def path_contributions(eq, net, tx_row, ig, m, K, seed, epoch=0, delta_t=0.0, fl
     if not flags & 2:
         cI, fb = 0 * cI, 0.0
     c = np.concatenate([cT + cI + fb * hmt, cT * Y + cI * Ys], -1)
+    if return_baseline:
+        return c, g_x, np.broadcast_to(np.asarray(fb * hmt, np.float64).reshape(-1), (len(m),)).copy()
     return c, g_x
 
 
-def path_contributions_hess(eq, net, tx_row, ig, m, K, seed, epoch=0, flags=3):
+def path_contributions_hess(eq, net, tx_row, ig, m, K, seed, epoch=0, flags=3, return_baseline=False):
     """Per-path rows of the Hessian-label estimator (labels_grad_hess): value/gradient c
     (len(m), 1+nx), Hessian h (len(m), nx*nx) whose means (+ g(x) in c[:, 0]) are the label.
-    flags (DPI_TERMINAL = 1 | DPI_INTEGRAL = 2): the estimators included."""
+    flags (DPI_TERMINAL = 1 | DPI_INTEGRAL = 2): the estimators included.  return_baseline: also the
+    baseline term f_b (T - t) of c[:, 0] per path (len(m),), as path_contributions."""
     t = float(tx_row[0])
     x = np.asarray(tx_row[1:], np.float64)[None]
     T, a, nx = eq.T, eq.alpha_sqrt, eq.nx
@@ -576,7 +590,35 @@ def path_contributions_hess(eq, net, tx_row, ig, m, K, seed, epoch=0, flags=3):
     aI = (T - t) * ((fp + fm - 2 * f_b) / 2 / (s - t))[:, 0]
     h = (kT * aT[:, None, None] * (N1[:, :, None] * N1[:, None, :] - np.eye(nx))
          + kI * aI[:, None, None] * (N2[:, :, None] * N2[:, None, :] - np.eye(nx)))
+    if return_baseline:
+        return c, h.reshape(len(m), nx * nx), g_x, np.full(len(m), kI * f_b * (T - t))
     return c, h.reshape(len(m), nx * nx), g_x
+
+
+def path_moments(eq, net, tx_row, ig, m_begin, m_end, K, seed, epoch=0, delta_t=0.0, flags=3, v=0, hessians=False,
+                 m_chunk=1024, return_rows=False):
+    """The fp64 reference of a label call's `moments` for one point: (sum of c, sum of c^2, g(x)) over the
+    MC indices [m_begin, m_end), c the per-path rows of path_contributions - every square formed per
+    path, before any sum.  hessians: the Hessian-label estimator (path_contributions_hess; no TD, no
+    SDGD), returning (sum c, sum c^2, sum h, sum h^2, g(x)) with h the per-path Hessian rows (nx*nx).
+    return_rows: the rows themselves, c (m_end - m_begin, 1+nx) [and h], after g(x)."""
+    assert not hessians or (delta_t == 0.0 and v == 0)
+    sums, g_x, rows = None, None, []
+    for m0 in range(m_begin, m_end, m_chunk):
+        m = np.arange(m0, min(m_end, m0 + m_chunk))
+        if hessians:
+            c, h, g_x = path_contributions_hess(eq, net, tx_row, ig, m, K, seed, epoch, flags=flags)
+            part = [c.sum(0), (c * c).sum(0), h.sum(0), (h * h).sum(0)]
+            rows.append((c, h))
+        else:
+            c, g_x = path_contributions(eq, net, tx_row, ig, m, K, seed, epoch, delta_t=delta_t, flags=flags, v=v)
+            part = [c.sum(0), (c * c).sum(0)]
+            rows.append((c,))
+        sums = part if sums is None else [a + b for a, b in zip(sums, part)]
+    out = tuple(sums) + (g_x,)
+    if return_rows:
+        out += tuple(np.concatenate(r) for r in zip(*rows))
+    return out
 
 
 def tree_sum_f32(values):

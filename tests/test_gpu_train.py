@@ -264,7 +264,11 @@ def test_picard_train_burgers_shipped_sizes_iteration1_known_answer(tmp_path):
     4096 x 101 labels against their closed-form expectation (_cha_iteration1_expectation) in units
     of each label's own Monte-Carlo standard error (from the label moments sum c, sum c^2): the mean
     squared z-score over all 413,696 entries must be 1 within 5 % and no |z| may exceed 6 — an MC
-    tolerance, not a fixed one.  Then the fit and evaluation run on those labels."""
+    tolerance, not a fixed one.  Then the fit and evaluation run on those labels.
+
+    The standard errors this test divides by come from the second half of `moments`, sum c^2, which
+    tests/test_gpu_moments.py pins to the fp64 oracle entry by entry (every entry within 1e-4, relative),
+    so a mean z^2 of 1 here is measured with a yardstick that is itself checked."""
     import numpy as np
     f = tmp_path / "burgers.yaml"
     f.write_text(BURGERS_SHIPPED.format(name=tmp_path / "run"))

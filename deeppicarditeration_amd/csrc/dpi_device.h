@@ -112,7 +112,7 @@ struct NetDev {
   const uint32_t* WU[4];     // (H, H)
   float wus[4];
   // mlp_hdiag_split's operand scales (powers of two from the host's calibration pass,
-  // dpi_kernels.hip x3_exponent): hsa[l] = store scale of a_l as the forward B operand of layer l + 1,
+  // dpi_net_image.h x3_exponent): hsa[l] = store scale of a_l as the forward B operand of layer l + 1,
   // hsc[l] = wus[l] / hsa[l - 1]; tangent z'_l (the raw accumulator) = z_l / hzs[l], the operand of
   // layer l + 1 = act'(a_l) hbs[l] z'_l
   float hsa[4], hsc[4], hzs[4], hbs[4];

@@ -152,7 +152,7 @@ namespace dpi {
 // an fp16 normal).  The weights are stored prescaled by a power of two 2^s (host, per matrix:
 // max |2^s W| in [0.5, 1)) so their residuals stay in fp16's normal range; the epilogue multiplies
 // by wscale = 2^-s (exact).  The activations and cotangents are stored prescaled too, by a power
-// of two 2^e per operand and network (dpi_kernels.hip x3_exponent: rms ~4, so their residuals stay
+// of two 2^e per operand and network (dpi_net_image.h x3_exponent: rms ~4, so their residuals stay
 // normal whatever the network's scale): wscale also carries the input's 2^-e (and, for EPI_DELU,
 // the output's 2^e), EPI_BIAS_ELU multiplies its output by oscale = 2^e, and EPI_DELU reads the
 // saved activation as a 2^-e = ascale.

@@ -1,6 +1,6 @@
-// Host helpers shared by the library's two host units (dpi_kernels.hip, dpi_net.hip): the error
-// string behind dpi_last_error, the HIP call check and the environment knobs.  One definition each
-// for both units, none of them an exported dynamic symbol.
+// Host helpers shared by the library's three host units (dpi_kernels.hip, dpi_net.hip, dpi_fit.hip):
+// the error string behind dpi_last_error, the HIP call check and the environment knobs.  One
+// definition each for all units, none of them an exported dynamic symbol.
 #pragma once
 #include <algorithm>
 #include <climits>
@@ -35,6 +35,6 @@ static inline double env_real(const char* name, double dflt, double lo, double h
   return e ? std::max(lo, std::min(hi, std::atof(e))) : dflt;
 }
 
-// dpi_label_prepare's records naming a destroyed handle (defined in dpi_kernels.hip, among the
-// extern "C" label calls)
+// dpi_label_prepare's records naming a destroyed handle (defined in dpi_kernels.hip, with the
+// workspace tags)
 extern "C" DPI_HIDDEN void prep_tags_drop(const void* owner);

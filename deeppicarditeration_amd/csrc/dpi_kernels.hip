@@ -14,8 +14,10 @@
 #include <algorithm>
 #include <atomic>
 #include <mutex>
+#include <optional>
 #include <string>
 #include <unordered_map>
+#include <utility>
 #include <vector>
 
 #include "../../include/dpi.h"
@@ -459,12 +461,20 @@ static bool gbm_noise_prep(dpi_problem p, dpi_net net) {
   static const bool on = env_int("DPI_GBM_PREP", 1) != 0;
   return on && p && net && net->d.kind == 1 && p->e.kind == DPI_EQ_GBM;
 }
+// the pairs for which dpi_label_prepare stages anything (the others' fused path kernels do it all)
+static bool stages_prepare(dpi_problem p, dpi_net net) {
+  return (net->d.kind == 2 || gbm_noise_prep(p, net)) && !(p->td_dt > 0.f);
+}
 // park: the pair's workspace holds the park (Route::park): DPI_PARK_MAX_BLOCKS rows of PARK_ROW floats,
 // one per path block of a call, in which a terminal-first block keeps its terminal sums across the
 // MLP (dpi_device.h paths_body).  A constant, so the workspace stays affine in n and M; a call with
 // more path blocks than rows leaves it unused and runs every block terminal-last.
 static bool park_pair(dpi_problem p, dpi_net net);
-static WsLayout ws_layout(dpi_net net, int n, int M, int F, bool noise = false, bool park = false) {
+// The optional regions a layout is asked for, by name: ws_layout(.., {.park = r.park}); {}: neither.
+struct WsRegions {
+  bool noise = false, park = false;
+};
+static WsLayout ws_layout(dpi_net net, int n, int M, int F, WsRegions want) {
   WsLayout w;
   // bx rows: the specialised image's H, or the general one's width cap (the wider of the two)
   const int H = (net && net->d.kind == 1) ? std::max(net->spec ? net->d.H : 0, net->gen ? net->g.H : 0) : 0;
@@ -491,9 +501,9 @@ static WsLayout ws_layout(dpi_net net, int n, int M, int F, bool noise = false, 
   // PISGradNet: the shared rollout's queue counter (256 B) and per-SIMD claim words
   w.noise = w.rq + ((net && net->d.kind == 2) ? 256 + (size_t)PIS_CLAIM_SLOTS * 4 : 0);
   const size_t nb4 = (size_t)((F - 1 + 3) / 4) * 4;
-  w.nq = w.noise + (noise ? al256((size_t)n * nbp * 2 * nb4 * P * 4) : 0);
+  w.nq = w.noise + (want.noise ? al256((size_t)n * nbp * 2 * nb4 * P * 4) : 0);
   // k_noise_shared's queue counter (256 B) and per-SIMD claim words
-  w.total = w.nq + (noise ? 256 + (size_t)PIS_CLAIM_SLOTS * 4 : 0);
+  w.total = w.nq + (want.noise ? 256 + (size_t)PIS_CLAIM_SLOTS * 4 : 0);
   // the general MLP family's stash (dpi_general.h): one slot per workgroup of its path launch, a fixed
   // count — it does not grow with n or M.  The last region, so every other offset stays where it was.
   // A gradient-head net parks nothing: no stash region.
@@ -505,7 +515,7 @@ static WsLayout ws_layout(dpi_net net, int n, int M, int F, bool noise = false, 
   // the park: the last region again, so every other offset stays where it was
   w.park = w.total;
   w.park_rows = 0;
-  if (park) {
+  if (want.park) {
     w.park_rows = (size_t)DPI_PARK_MAX_BLOCKS;
     w.park = al256(w.total);
     w.total = w.park + w.park_rows * PARK_ROW * 4;
@@ -650,29 +660,18 @@ static PisRows pis_chain_x3(const NetPisDev& pd, float* rows, int R, hipStream_t
   // the VJP chain as one launch with the activations in LDS (dpi_pisnet.h), where the shape fits
   if (vjp && R > 0 && pis_fused_on() && pis_fused_fits(pd, L)) {
     const dim3 grid((R + PN_BM - 1) / PN_BM), block(PN_THREADS);
-    // DPI_PIS_NT: 2 (default) non-temporal row loads, plain stores; 1 both non-temporal; 0 neither
-    const int nt = env_int("DPI_PIS_NT", 2);
-    const int ntm = nt == 1 ? 3 : nt == 0 ? 0 : 1;
+    // row loads non-temporal, stores plain (k_pis_net's NTM = 1)
     hipEvent_t t0, t1;
     take_timer(t0, t1);
-    auto launch = [&](auto ntc, auto nlc) {
-      hipExtLaunchKernelGGL((k_pis_net<decltype(ntc)::value, decltype(nlc)::value>), grid, block, 0, st, t0, t1, 0, pd,
-                            rows, L, R);
+    auto launch = [&](auto nlc) {
+      hipExtLaunchKernelGGL((k_pis_net<1, decltype(nlc)::value>), grid, block, 0, st, t0, t1, 0, pd, rows, L, R);
     };
-    auto by_depth = [&](auto ntc) {
-      switch (pd.L) {
-        case 1: launch(ntc, std::integral_constant<int, 1>{}); break;
-        case 2: launch(ntc, std::integral_constant<int, 2>{}); break;
-        case 3: launch(ntc, std::integral_constant<int, 3>{}); break;
-        default: launch(ntc, std::integral_constant<int, 4>{}); break;
-      }
-    };
-    if (ntm == 1)
-      by_depth(std::integral_constant<int, 1>{});
-    else if (ntm == 3)
-      by_depth(std::integral_constant<int, 3>{});
-    else
-      by_depth(std::integral_constant<int, 0>{});
+    switch (pd.L) {
+      case 1: launch(std::integral_constant<int, 1>{}); break;
+      case 2: launch(std::integral_constant<int, 2>{}); break;
+      case 3: launch(std::integral_constant<int, 3>{}); break;
+      default: launch(std::integral_constant<int, 4>{}); break;
+    }
     return L;
   }
   int Kp = L.INP;
@@ -749,13 +748,13 @@ static PisRows pis_chain(const NetPisDev& pd, float* rows, int R, hipStream_t st
 
 extern "C" size_t dpi_workspace_bytes(dpi_problem p, dpi_net net, int n, int M) {
   if (!p || n < 0 || M < 0) return 0;
-  return ws_layout(net, n, M, 1 + p->e.nx, false, park_pair(p, net)).total;
+  return ws_layout(net, n, M, 1 + p->e.nx, {.park = park_pair(p, net)}).total;
 }
 // + the staged noise sums of a GBM MLP net's prepared calls (the last region of the layout, so a
 // plain call's offsets are the same)
 extern "C" size_t dpi_workspace_bytes_prepared(dpi_problem p, dpi_net net, int n, int M) {
   if (!p || n < 0 || M < 0) return 0;
-  return ws_layout(net, n, M, 1 + p->e.nx, gbm_noise_prep(p, net), park_pair(p, net)).total;
+  return ws_layout(net, n, M, 1 + p->e.nx, {.noise = gbm_noise_prep(p, net), .park = park_pair(p, net)}).total;
 }
 
 // the counters of draws 1-3 (k_sample_points, k_baseline's in-block sampling)
@@ -821,6 +820,104 @@ static int route_call(dpi_problem p, dpi_net net, RouteCall call, Route* r) {
 }
 static bool park_pair(dpi_problem p, dpi_net net) { return p && net && pair_route(p, net, ROUTE_PATHS).park; }
 
+// One label call as its entry point received it: the dpi_label_*, dpi_generate_* and
+// dpi_sample_with_gradients entry points fill it once, field by field, and the host side passes it on
+// whole.  What follows from it alone is computed here and nowhere else.
+struct LabelCall {
+  dpi_problem p = nullptr;
+  dpi_net net = nullptr;
+  const float* tx = nullptr;
+  int n = 0, M = 0, K = 0;
+  uint64_t seed = 0;
+  uint32_t epoch = 0, point_base = 0;
+  int m_begin = 0, m_end = 0, flags = 0;
+  void* ws = nullptr;
+  size_t ws_bytes = 0;
+  void* stream = nullptr;
+  // the outputs the entry point has: the sums, and the finalized labels y clipped at bound
+  float *moments = nullptr, *hessian_sums = nullptr, *y = nullptr;
+  float bound = 0.f;
+  // the kind of entry point: the route it asks for; dpi_label_prepare stages only (it has no outputs)
+  RouteCall call = ROUTE_PATHS;
+  bool stage_only = false;
+  bool hess() const { return call == ROUTE_HESS; }
+  bool prepared() const { return stage_only || (flags & DPI_PREPARED); }  // dpi_label_prepare, or the call it feeds
+  bool noise() const { return prepared() && gbm_noise_prep(p, net); }    // ... with the noise staging region
+  // floats per row of y: the first-order labels, then the Hessian's
+  int ystride() const { return 1 + p->e.nx + (hess() ? p->e.nx * p->e.nx : 0); }
+  char* base() const { return (char*)ws; }
+  hipStream_t st() const { return (hipStream_t)stream; }
+};
+
+// ---- the workspace tag: what the host knows of a workspace, one record per pointer under one mutex.
+// base_n: the fused reduce (k_paths' last block per point) counts blocks on per-point tickets that the
+// baseline launch zeroes and the last block resets.  The tag holds the point count of the baseline
+// enqueued on the workspace, and a fused label call on a workspace without one fails instead of running
+// a reduce whose tickets hold garbage (it would never fire and leave the labels unwritten).
+// prep, the DPI_PREPARED contract: a prepared label call trusts that dpi_label_prepare staged the first
+// chunk in the same workspace with the same arguments.  dpi_label_prepare records them (host side: no
+// device read, no sync); the prepared call must match them and consumes the record, so a mismatched or
+// repeated call fails with DPI_ERR_ARG instead of producing labels from another batch's rollout.  The
+// GEMM mode is among them (split and fp32 rows differ in layout): a precision switch between prepare and
+// the prepared call fails instead of reading rows laid out the other way.
+struct PrepTag {
+  const void *p, *net, *tx;
+  int n, M, K, m_begin, m_end, flags, mode;
+  uint64_t seed;
+  uint32_t epoch, point_base;
+  size_t ws_bytes;
+  bool operator==(const PrepTag& o) const {
+    return p == o.p && net == o.net && tx == o.tx && n == o.n && M == o.M && K == o.K && m_begin == o.m_begin &&
+           m_end == o.m_end && flags == o.flags && mode == o.mode && seed == o.seed && epoch == o.epoch &&
+           point_base == o.point_base && ws_bytes == o.ws_bytes;
+  }
+};
+static PrepTag prep_tag(const LabelCall& c) {
+  return PrepTag{.p = c.p, .net = c.net, .tx = c.tx, .n = c.n, .M = c.M, .K = c.K, .m_begin = c.m_begin,
+                 .m_end = c.m_end, .flags = c.flags & DPI_BOTH, .mode = pis_x3(c.net) ? 1 : 0, .seed = c.seed,
+                 .epoch = c.epoch, .point_base = c.point_base, .ws_bytes = c.ws_bytes};
+}
+struct WsTag {
+  int base_n = 0;               // points of the baseline enqueued on the workspace (0: none)
+  std::optional<PrepTag> prep;  // dpi_label_prepare's record, until a label call consumes or invalidates it
+};
+static std::mutex g_ws_mu;
+static std::unordered_map<const void*, WsTag>& ws_tags() {
+  static std::unordered_map<const void*, WsTag> m;
+  return m;
+}
+static void base_tag_set(const void* ws, int n) {
+  std::lock_guard<std::mutex> g(g_ws_mu);
+  ws_tags()[ws].base_n = n;
+}
+static bool base_tag_ok(const void* ws, int n) {
+  std::lock_guard<std::mutex> g(g_ws_mu);
+  auto it = ws_tags().find(ws);
+  return it != ws_tags().end() && it->second.base_n == n;
+}
+static void prep_tag_set(const LabelCall& c) {
+  std::lock_guard<std::mutex> g(g_ws_mu);
+  ws_tags()[c.ws].prep = prep_tag(c);
+}
+// The workspace's prepare record, and the record gone.
+static std::optional<PrepTag> prep_tag_take(const void* ws) {
+  std::lock_guard<std::mutex> g(g_ws_mu);
+  auto it = ws_tags().find(ws);
+  return it == ws_tags().end() ? std::nullopt : std::exchange(it->second.prep, std::nullopt);
+}
+void prep_tags_drop(const void* owner) {
+  std::lock_guard<std::mutex> g(g_ws_mu);
+  for (auto& kv : ws_tags())
+    if (kv.second.prep && (kv.second.prep->p == owner || kv.second.prep->net == owner)) kv.second.prep.reset();
+}
+extern "C" int dpi_workspace_forget(const void* ws, size_t ws_bytes) {
+  const char *lo = (const char*)ws, *hi = lo + ws_bytes;
+  std::lock_guard<std::mutex> g(g_ws_mu);
+  for (auto it = ws_tags().begin(); it != ws_tags().end();)
+    it = ((const char*)it->first >= lo && (const char*)it->first < hi) ? ws_tags().erase(it) : std::next(it);
+  return 0;
+}
+
 // The launch of the route's unit.  A unit that cannot serve the call it was chosen for is a bug in the
 // route: reported here, for every entry point.
 static int launch_unit(const dpi_problem_s* p, const dpi_net_s* net, const Launch& q) {
@@ -847,13 +944,13 @@ static Launch baseline_launch(const Route& r, const float* tx, int n, void* ws, 
   q.st = st;
   return q;
 }
-static Launch path_launch(const Route& r, const PathArgs& a, int nblocks, void* ws, const WsLayout& w, hipStream_t st) {
+static Launch path_launch(const Route& r, const PathArgs& a, int nblocks, const LabelCall& c, const WsLayout& w) {
   Launch q;
   q.unit = r.unit;
   q.a = &a;
   q.nblocks = nblocks;
-  q.st = st;
-  if (r.stash) q.stash = (floatx4*)((char*)ws + w.stash);
+  q.st = c.st();
+  if (r.stash) q.stash = (floatx4*)(c.base() + w.stash);
   return q;
 }
 
@@ -894,14 +991,6 @@ static int pis_rollout_unroll() {
   return v;
 }
 
-// Prepare-stream rollout in grids of DPI_PIS_PREP_PER_CU path sets per CU (0 / unset: one grid).
-// Round 3's k_gemm_x3 chain needed bounded grids (3 per CU) so the rollout did not pack whole CUs;
-// the one-wave rollout beside k_pis_net runs as one grid by default.
-static int pis_prep_per_cu() {
-  static const int v = env_int("DPI_PIS_PREP_PER_CU", 0, 0, 64);
-  return v;
-}
-
 // The prepare stream's rollout as the per-SIMD-capped work queue (k_pis_rollout_shared), launched
 // with DPI_PIS_PREP_SHARED (default 2) waves per SIMD more than it keeps; 0: the plain grid.
 static int pis_prep_shared() {
@@ -922,8 +1011,14 @@ static int pis_prep_sets(int g) {
 
 // prepared: dpi_label_prepare already ran the first chunk's rollout and baseline rows (same
 // arguments, same workspace); prepare_only: run just those (dpi_label_prepare).
-static int pis_paths(dpi_problem p, dpi_net net, const float* tx, int n, int K, const PathArgs& a, const WsLayout& w,
-                     char* b, hipStream_t st, bool prepared = false, bool prepare_only = false) {
+static int pis_paths(const LabelCall& c, const PathArgs& a, const WsLayout& w) {
+  const dpi_problem p = c.p;
+  const dpi_net net = c.net;
+  const float* tx = c.tx;
+  const int n = c.n, K = c.K;
+  char* b = c.base();
+  hipStream_t st = c.st();
+  const bool prepare_only = c.stage_only, prepared = !prepare_only && c.prepared();
   int rc = pis_check(p);
   if (rc) return rc;
   float* rows = (float*)(b + w.rows);
@@ -960,19 +1055,18 @@ static int pis_paths(dpi_problem p, dpi_net net, const float* tx, int n, int K, 
         }
       }
       const int gend = prepare_only ? gprep : g;
-      int step = gend - gbeg;
-      if (prepare_only && pis_prep_per_cu() > 0) step = pis_prep_per_cu() * cu_count();
-      for (int bx0 = gbeg; bx0 < gend; bx0 += step) {  // two one-wave blocks (terminal, integral) per path set
-        const dim3 grid(2 * PIS_PARTS * std::min(step, gend - bx0)), block(P);  // (path, dim part) tasks
-        if (pis_rollout_unroll() == 4)
-          hipLaunchKernelGGL((k_pis_rollout<DPI_EQ_OU, X3, 4>), grid, block, 0, st, p->e, net->pis, tx, g0, a.nbp,
-                             a.m_begin, K, a.flags, a.k0, a.k1, a.c3t, a.c3s, a.c3i, a.point_base, rows, L, stage,
-                             dt, bx0);
-        else
-          hipLaunchKernelGGL((k_pis_rollout<DPI_EQ_OU, X3, 2>), grid, block, 0, st, p->e, net->pis, tx, g0, a.nbp,
-                             a.m_begin, K, a.flags, a.k0, a.k1, a.c3t, a.c3s, a.c3i, a.point_base, rows, L, stage,
-                             dt, bx0);
-      }
+      if (gend <= gbeg) return;
+      // two one-wave blocks (terminal, integral) per path set of [gbeg, gend): (path, dim part) tasks
+      const dim3 grid(2 * PIS_PARTS * (gend - gbeg)), block(P);
+      auto launch = [&](auto unr) {
+        hipLaunchKernelGGL((k_pis_rollout<DPI_EQ_OU, X3, decltype(unr)::value>), grid, block, 0, st, p->e, net->pis, tx,
+                           g0, a.nbp, a.m_begin, K, a.flags, a.k0, a.k1, a.c3t, a.c3s, a.c3i, a.point_base, rows, L,
+                           stage, dt, gbeg);
+      };
+      if (pis_rollout_unroll() == 4)
+        launch(std::integral_constant<int, 4>{});
+      else
+        launch(std::integral_constant<int, 2>{});
     };
     const bool base = g0 == 0;
     float* brows = rows + (size_t)g * P * L.stride;
@@ -1011,33 +1105,13 @@ static int pis_paths(dpi_problem p, dpi_net net, const float* tx, int n, int K, 
   return 0;
 }
 
-// The fused reduce (k_paths' last block per point) counts blocks on per-point tickets that the
-// baseline launch zeroes and the last block resets.  The host records which workspaces had a
-// baseline of how many points enqueued on them, and a fused label call on a workspace without one
-// fails instead of running a reduce whose tickets hold garbage (it would never fire and leave the
-// labels unwritten).
-static std::mutex g_base_mu;
-static std::unordered_map<const void*, int>& base_tags() {
-  static std::unordered_map<const void*, int> m;
-  return m;
-}
-static void base_tag_set(const void* ws, int n) {
-  std::lock_guard<std::mutex> g(g_base_mu);
-  base_tags()[ws] = n;
-}
-static bool base_tag_ok(const void* ws, int n) {
-  std::lock_guard<std::mutex> g(g_base_mu);
-  auto it = base_tags().find(ws);
-  return it != base_tags().end() && it->second == n;
-}
-
 int dpi_point_baseline(dpi_problem p, dpi_net net, const float* tx, int n, void* ws, size_t ws_bytes, void* stream) {
   Route r;
   int rc = route_call(p, net, ROUTE_BASELINE, &r);
   if (rc) return rc;
   if (n < 0 || (n && (!tx || !ws))) return fail(DPI_ERR_ARG, "point_baseline: bad arguments");
   if (n == 0) return 0;
-  const WsLayout w = ws_layout(net, n, 0, 1 + p->e.nx);
+  const WsLayout w = ws_layout(net, n, 0, 1 + p->e.nx, {});
   if (ws_bytes < w.partial) return fail(DPI_ERR_WORKSPACE, "workspace too small");
   if (net->d.kind == 2) return pis_baseline(p);
   if ((rc = launch_unit(p, net, baseline_launch(r, tx, n, ws, w, (hipStream_t)stream)))) return rc;
@@ -1131,49 +1205,44 @@ int dpi_launch_units(int* tail, int* grid, int* launches) {
   return 0;
 }
 
-static size_t hess_extra(int n, int M, int nx, size_t* moff);
-// Validates a label-moments call and fills its PathArgs (shared by dpi_label_moments,
-// dpi_label_prepare and, with ROUTE_HESS, the Hessian-label calls: their own error texts, and the
-// Hessian block sums and moments behind the layout, hess_extra).  Returns 0, or the error; *w receives
-// the workspace layout, *r the call's route.
-static int label_args(dpi_problem p, dpi_net net, const float* tx, int n, int M, int K, uint64_t seed,
-                      uint32_t epoch, uint32_t point_base, int m_begin, int m_end, int flags, bool need_moments,
-                      const float* moments, void* ws, size_t ws_bytes, WsLayout* w, PathArgs* pa, Route* r,
-                      RouteCall call = ROUTE_PATHS) {
-  const bool prepared = !need_moments || (flags & DPI_PREPARED);  // dpi_label_prepare, or its prepared call
-  const bool hess = call == ROUTE_HESS;
-  int rc = route_call(p, net, call, r);
+static size_t hess_extra(int n, int M, int nx, size_t* moff = nullptr);
+// Validates a label call and fills its PathArgs (the first-order calls, dpi_label_prepare and, with
+// ROUTE_HESS, the Hessian-label calls: their own error texts, and the Hessian block sums and moments
+// behind the layout, hess_extra).  Returns 0, or the error; *w receives the workspace layout, *r the
+// call's route.
+static int label_args(const LabelCall& c, WsLayout* w, PathArgs* pa, Route* r) {
+  const bool hess = c.hess(), need_moments = !c.stage_only;
+  const int n = c.n, M = c.M;
+  int rc = route_call(c.p, c.net, c.call, r);
   if (rc) return rc;
-  if (n < 0 || (n && (!tx || !ws || (need_moments && !moments))) || K < 1 || M < 1 || m_begin < 0 || m_end > M ||
-      m_end <= m_begin || (m_begin % P) || ((m_end % P) && m_end != M) || !(flags & DPI_BOTH) ||
-      (flags & ~(DPI_BOTH | DPI_PREPARED)) || epoch > 0xFFFFFFu)
+  if (n < 0 || (n && (!c.tx || !c.ws || (need_moments && !c.moments))) || c.K < 1 || M < 1 || c.m_begin < 0 ||
+      c.m_end > M || c.m_end <= c.m_begin || (c.m_begin % P) || ((c.m_end % P) && c.m_end != M) ||
+      !(c.flags & DPI_BOTH) || (c.flags & ~(DPI_BOTH | DPI_PREPARED)) || c.epoch > 0xFFFFFFu)
     return fail(DPI_ERR_ARG,
                 hess ? "Hessian labels: bad arguments (m range within [0, M], m_begin a multiple of 64, m_end a "
                        "multiple of 64 or M; K >= 1, flags in DPI_TERMINAL | DPI_INTEGRAL | DPI_PREPARED)"
                      : "label_moments: bad arguments (m range within [0, M], m_begin a multiple of 64, m_end a "
                        "multiple of 64 or M; K >= 1)");
   if (n == 0) return 0;
-  const int F = 1 + p->e.nx;
+  const dpi_problem p = c.p;
   // whole 64-path blocks; the lanes of the last one at m >= m_end are dead (PathArgs::m_end)
-  const int nbp = (m_end - m_begin + P - 1) / P;
+  const int nbp = (c.m_end - c.m_begin + P - 1) / P;
   if (nbp > DPI_PATHS_PER_CALL_MAX / P)
     return fail(DPI_ERR_ARG, std::string(hess ? "Hessian labels" : "label_moments") +
                                  ": at most DPI_PATHS_PER_CALL_MAX paths per call");
   // the noise staging region only for dpi_label_prepare and the DPI_PREPARED call it feeds
-  const bool noise = prepared && gbm_noise_prep(p, net);
-  *w = ws_layout(net, n, M, F, noise, r->park);
-  if (hess) {
-    size_t moff;
-    if (ws_bytes < al256(w->total) + hess_extra(n, M, p->e.nx, &moff))
-      return fail(DPI_ERR_WORKSPACE, noise ? "workspace too small (dpi_workspace_bytes_hessians_prepared)"
-                                           : "workspace too small (dpi_workspace_bytes_hessians)");
-  } else if (ws_bytes < w->total)
-    return fail(DPI_ERR_WORKSPACE, prepared ? "workspace too small (prepared calls: dpi_workspace_bytes_prepared)"
-                                            : "workspace too small");
-  char* b = (char*)ws;
+  const bool noise = c.noise();
+  *w = ws_layout(c.net, n, M, 1 + p->e.nx, {.noise = noise, .park = r->park});
+  if (hess && c.ws_bytes < al256(w->total) + hess_extra(n, M, p->e.nx))
+    return fail(DPI_ERR_WORKSPACE, noise ? "workspace too small (dpi_workspace_bytes_hessians_prepared)"
+                                         : "workspace too small (dpi_workspace_bytes_hessians)");
+  if (!hess && c.ws_bytes < w->total)
+    return fail(DPI_ERR_WORKSPACE, c.prepared() ? "workspace too small (prepared calls: dpi_workspace_bytes_prepared)"
+                                                : "workspace too small");
+  char* b = c.base();
   PathArgs& a = *pa;
   std::memset(&a, 0, sizeof(a));
-  a.tx = tx;
+  a.tx = c.tx;
   a.gx = (const float*)(b + w->gx);
   a.fb = (const float*)(b + w->fb);
   a.bx = (const float*)(b + w->bx);
@@ -1181,19 +1250,19 @@ static int label_args(dpi_problem p, dpi_net net, const float* tx, int n, int M,
   a.partial = (float*)(b + w->partial);
   a.n = n;
   a.nbp = nbp;
-  a.m_begin = m_begin;
-  a.m_end = m_end;
-  a.K = K;
-  a.flags = flags & DPI_BOTH;
-  a.k0 = (uint32_t)seed;
-  a.k1 = (uint32_t)(seed >> 32);
-  a.c3t = DPI_TAG_TERM | (epoch << 8);
-  a.c3s = DPI_TAG_S | (epoch << 8);
-  a.c3i = DPI_TAG_INT | (epoch << 8);
-  a.c3q = DPI_TAG_SDGD | (epoch << 8);
-  a.point_base = point_base;
+  a.m_begin = c.m_begin;
+  a.m_end = c.m_end;
+  a.K = c.K;
+  a.flags = c.flags & DPI_BOTH;
+  a.k0 = (uint32_t)c.seed;
+  a.k1 = (uint32_t)(c.seed >> 32);
+  a.c3t = DPI_TAG_TERM | (c.epoch << 8);
+  a.c3s = DPI_TAG_S | (c.epoch << 8);
+  a.c3i = DPI_TAG_INT | (c.epoch << 8);
+  a.c3q = DPI_TAG_SDGD | (c.epoch << 8);
+  a.point_base = c.point_base;
   a.order = path_order();
-  a.split = mlp_split(net) ? 1 : 0;
+  a.split = mlp_split(c.net) ? 1 : 0;
   // the split specialised instances' park, when it holds a row for every path block of this call
   if (r->parks && (size_t)n * nbp <= w->park_rows)
     a.park = (float*)(b + w->park);
@@ -1203,55 +1272,49 @@ static int label_args(dpi_problem p, dpi_net net, const float* tx, int n, int M,
 }
 
 // Arms the fused reduce of a path launch: k_paths' last block per point counts on the workspace's
-// tickets, reduces the point's partials into `moments` and finalizes the labels into y.
-static void arm_fused_reduce(PathArgs& a, dpi_net net, void* ws, const WsLayout& w, int M, int flags, float* moments,
-                             float* y, float bound) {
-  a.tickets = (int*)((char*)ws + w.tk);
-  a.rd_moments = moments;
-  a.rd_y = y;
-  a.rd_status = net_status(net);
-  a.rd_invM = 1.0f / (float)M;
-  a.rd_bound = bound;
-  a.rd_add_g = (flags & DPI_TERMINAL) ? 1 : 0;
+// tickets, reduces the point's partials into the call's moments and finalizes the labels into its y.
+static void arm_fused_reduce(PathArgs& a, const LabelCall& c, const WsLayout& w) {
+  a.tickets = (int*)(c.base() + w.tk);
+  a.rd_moments = c.moments;
+  a.rd_y = c.y;
+  a.rd_status = net_status(c.net);
+  a.rd_invM = 1.0f / (float)c.M;
+  a.rd_bound = c.bound;
+  a.rd_add_g = (c.flags & DPI_TERMINAL) ? 1 : 0;
 }
 
-static bool stages_prepare(dpi_problem p, dpi_net net);
-static int moments_impl(dpi_problem p, dpi_net net, const float* tx, int n, int M, int K, uint64_t seed,
-                        uint32_t epoch, uint32_t point_base, int m_begin, int m_end, int flags, float* moments,
-                        void* ws, size_t ws_bytes, void* stream, float* y, float bound) {
+// The separate reduce of a path launch's block sums: the moments and, where the call has a y, the
+// first-order labels in its rows.
+static void launch_reduce(const LabelCall& c, const PathArgs& a) {
+  const int F = 1 + c.p->e.nx;
+  hipLaunchKernelGGL(k_reduce, dim3(c.n, (2 * F + 3) / 4), dim3(256), 0, c.st(), a.partial, c.n, F, a.nbp, c.moments,
+                     a.gx, 1.0f / (float)c.M, (c.flags & DPI_TERMINAL) ? 1 : 0, c.bound, c.y, c.ystride(),
+                     net_status(c.net));
+}
+
+static int moments_impl(const LabelCall& c) {
   WsLayout w;
   PathArgs a;
   Route r;
-  int rc = label_args(p, net, tx, n, M, K, seed, epoch, point_base, m_begin, m_end, flags, true, moments, ws, ws_bytes,
-                      &w, &a, &r);
-  if (rc || n == 0) return rc;
-  const int F = 1 + p->e.nx, nbp = a.nbp;
-  char* b = (char*)ws;
-  float* partial = a.partial;
-  hipStream_t st = (hipStream_t)stream;
-  if (net->d.kind == 2) {
-    if ((rc = pis_paths(p, net, tx, n, K, a, w, b, st, (flags & DPI_PREPARED) != 0))) return rc;
+  int rc = label_args(c, &w, &a, &r);
+  if (rc || c.n == 0) return rc;
+  if (c.net->d.kind == 2) {
+    if ((rc = pis_paths(c, a, w))) return rc;
   } else {
-    Launch q = path_launch(r, a, n * nbp, ws, w, st);
-    take_timer(q.t0, q.t1);
-    if ((flags & DPI_PREPARED) && stages_prepare(p, net)) a.noise = (const float*)(b + w.noise);
-    if (nbp <= 64 && fused_reduce_on()) {  // k_paths' last block per point reduces and finalizes
-      if (!base_tag_ok(ws, n))
+    Launch q = path_launch(r, a, c.n * a.nbp, c, w);
+    if (c.noise() && stages_prepare(c.p, c.net)) a.noise = (const float*)(c.base() + w.noise);
+    if (a.nbp <= 64 && fused_reduce_on()) {  // k_paths' last block per point reduces and finalizes
+      if (!base_tag_ok(c.ws, c.n))
         return fail(DPI_ERR_ARG, "label_moments: no dpi_point_baseline / dpi_sample_points_baseline of these n points "
                                  "was enqueued on this workspace (the fused reduce's tickets are zeroed there)");
-      arm_fused_reduce(a, net, ws, w, M, flags, moments, y, bound);
+      arm_fused_reduce(a, c, w);
     }
-    arm_tail(a, r, p, w);
-    if ((rc = launch_units(p, net, q, a, 0))) return rc;
-    if (a.tickets) {
-      HIPCHK(hipGetLastError());
-      return 0;
-    }
+    take_timer(q.t0, q.t1);  // behind the last refusal: a refused call leaves the timer armed
+    arm_tail(a, r, c.p, w);
+    if ((rc = launch_units(c.p, c.net, q, a, 0))) return rc;
   }
   HIPCHK(hipGetLastError());
-  hipLaunchKernelGGL(k_reduce, dim3(n, (2 * F + 3) / 4), dim3(256), 0, st, partial, n, F, nbp, moments,
-                     (const float*)(b + w.gx), 1.0f / (float)M, (flags & DPI_TERMINAL) ? 1 : 0, bound, y, F,
-                     net_status(net));
+  if (!a.tickets) launch_reduce(c, a);  // else the path launch reduced
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -1276,31 +1339,31 @@ int dpi_sample_with_gradients(dpi_problem p, dpi_net net, int n, int M, int K, u
     return fail(DPI_ERR_ARG, "sample_with_gradients: bad arguments (n >= 0, M, K >= 1, t_factors in [0, 4096])");
   if (n == 0) return 0;
   if (!tx || !y || !moments) return fail(DPI_ERR_ARG, "sample_with_gradients: null tx, y or moments");
-  const int F = 1 + p->e.nx;
-  const WsLayout w = ws_layout(net, n, M, F, false, r.park);
+  const WsLayout w = ws_layout(net, n, M, 1 + p->e.nx, {.park = r.park});
   if (!ws || ws_bytes < w.total) return fail(DPI_ERR_WORKSPACE, "workspace too small");
   if (net->d.kind == 2) {
     if ((rc = dpi_sample_points_t(p, n, seed, epoch, point_base, eps, t_factors, tx, stream))) return rc;
     return dpi_generate_with_gradients(p, net, tx, n, M, K, seed, epoch, point_base, flags, sample_bound, y, moments, ws,
                                        ws_bytes, stream);
   }
+  LabelCall c{.p = p, .net = net, .tx = tx, .n = n, .M = M, .K = K, .seed = seed, .epoch = epoch,
+              .point_base = point_base, .m_begin = 0, .m_end = M, .flags = flags, .ws = ws, .ws_bytes = ws_bytes,
+              .stream = stream, .moments = moments, .y = y, .bound = sample_bound};
   if (r.fused && (M + P - 1) / P <= 64 && fused_reduce_on() && fused_base_on()) {
     WsLayout wl;
     PathArgs a;
-    if ((rc = label_args(p, net, tx, n, M, K, seed, epoch, point_base, 0, M, flags, true, moments, ws, ws_bytes, &wl,
-                         &a, &r, ROUTE_FUSED)))
-      return rc;
-    char* b = (char*)ws;
-    arm_fused_reduce(a, net, ws, wl, M, flags, moments, y, sample_bound);
+    c.call = ROUTE_FUSED;
+    if ((rc = label_args(c, &wl, &a, &r))) return rc;
+    arm_fused_reduce(a, c, wl);
     FusedBase fb{};
     fb.nbase = n;
-    fb.rec = (float*)(b + wl.rec);
-    fb.ready = (unsigned long long*)(b + wl.ready);
+    fb.rec = (float*)(c.base() + wl.rec);
+    fb.ready = (unsigned long long*)(c.base() + wl.ready);
     fb.ready_seq = next_ready_seq();
     fb.smp = sample_spec(p, seed, epoch, point_base, eps, t_factors, tx);
-    Launch q = path_launch(r, a, n + n * a.nbp, ws, wl, (hipStream_t)stream);
+    Launch q = path_launch(r, a, n + n * a.nbp, c, wl);
     q.fbase = &fb;
-    take_timer(q.t0, q.t1);
+    take_timer(q.t0, q.t1);  // behind label_args' late refusal
     arm_tail(a, r, p, wl);
     if ((rc = launch_units(p, net, q, a, n))) return rc;
     HIPCHK(hipGetLastError());
@@ -1309,8 +1372,7 @@ int dpi_sample_with_gradients(dpi_problem p, dpi_net net, int n, int M, int K, u
   }
   if ((rc = dpi_sample_points_baseline(p, net, n, seed, epoch, point_base, eps, t_factors, tx, ws, ws_bytes, stream)))
     return rc;
-  return moments_impl(p, net, tx, n, M, K, seed, epoch, point_base, 0, M, flags, moments, ws, ws_bytes, stream, y,
-                      sample_bound);
+  return moments_impl(c);
 }
 
 // The points (dpi_sample_points_t's draws) and their baseline (dpi_point_baseline) in ONE launch
@@ -1327,7 +1389,7 @@ int dpi_sample_points_baseline(dpi_problem p, dpi_net net, int n, uint64_t seed,
     if ((rc = dpi_sample_points_t(p, n, seed, epoch, point_base, eps, t_factors, tx, stream))) return rc;
     return dpi_point_baseline(p, net, tx, n, ws, ws_bytes, stream);
   }
-  const WsLayout w = ws_layout(net, n, 0, 1 + p->e.nx);
+  const WsLayout w = ws_layout(net, n, 0, 1 + p->e.nx, {});
   if (ws_bytes < w.partial) return fail(DPI_ERR_WORKSPACE, "workspace too small");
   Launch q = baseline_launch(r, tx, n, ws, w, (hipStream_t)stream);
   q.smp = sample_spec(p, seed, epoch, point_base, eps, t_factors, tx);
@@ -1337,103 +1399,40 @@ int dpi_sample_points_baseline(dpi_problem p, dpi_net net, int n, uint64_t seed,
   return 0;
 }
 
-// The DPI_PREPARED contract: a prepared label-moments call trusts that dpi_label_prepare staged
-// the first chunk in the same workspace with the same arguments.  dpi_label_prepare records the
-// arguments per workspace (host side: no device read, no sync); the prepared call must match them
-// and consumes the record, so a mismatched or repeated call fails with DPI_ERR_ARG instead of
-// producing labels from another batch's rollout.
-// The tag also records the GEMM mode the rows were staged under (split and fp32 rows differ in
-// layout): a precision switch between prepare and the prepared call fails instead of reading rows
-// laid out the other way.
-struct PrepTag {
-  const void *p, *net, *tx;
-  int n, M, K, m_begin, m_end, flags, mode;
-  uint64_t seed;
-  uint32_t epoch, point_base;
-  size_t ws_bytes;
-  bool operator==(const PrepTag& o) const {
-    return p == o.p && net == o.net && tx == o.tx && n == o.n && M == o.M && K == o.K && m_begin == o.m_begin &&
-           m_end == o.m_end && flags == o.flags && mode == o.mode && seed == o.seed && epoch == o.epoch &&
-           point_base == o.point_base && ws_bytes == o.ws_bytes;
-  }
-};
-static std::mutex g_prep_mu;
-static std::unordered_map<const void*, PrepTag>& prep_tags() {
-  static std::unordered_map<const void*, PrepTag> m;
-  return m;
-}
-
-void prep_tags_drop(const void* owner) {
-  std::lock_guard<std::mutex> g(g_prep_mu);
-  for (auto it = prep_tags().begin(); it != prep_tags().end();)
-    it = (it->second.p == owner || it->second.net == owner) ? prep_tags().erase(it) : std::next(it);
-}
-
-extern "C" int dpi_workspace_forget(const void* ws, size_t ws_bytes) {
-  const char *lo = (const char*)ws, *hi = lo + ws_bytes;
-  auto inside = [&](const void* a) { return (const char*)a >= lo && (const char*)a < hi; };
-  {
-    std::lock_guard<std::mutex> g(g_base_mu);
-    for (auto it = base_tags().begin(); it != base_tags().end();) it = inside(it->first) ? base_tags().erase(it) : std::next(it);
-  }
-  std::lock_guard<std::mutex> g(g_prep_mu);
-  for (auto it = prep_tags().begin(); it != prep_tags().end();) it = inside(it->first) ? prep_tags().erase(it) : std::next(it);
-  return 0;
-}
-
-static bool stages_prepare(dpi_problem p, dpi_net net) {
-  return (net->d.kind == 2 || gbm_noise_prep(p, net)) && !(p->td_dt > 0.f);
-}
-
 int dpi_label_prepare(dpi_problem p, dpi_net net, const float* tx, int n, int M, int K, uint64_t seed, uint32_t epoch,
                       uint32_t point_base, int m_begin, int m_end, int flags, void* ws, size_t ws_bytes, void* stream) {
+  const LabelCall c{.p = p, .net = net, .tx = tx, .n = n, .M = M, .K = K, .seed = seed, .epoch = epoch,
+                    .point_base = point_base, .m_begin = m_begin, .m_end = m_end, .flags = flags & DPI_BOTH, .ws = ws,
+                    .ws_bytes = ws_bytes, .stream = stream, .stage_only = true};
   WsLayout w;
   PathArgs a;
   Route r;
-  int rc = label_args(p, net, tx, n, M, K, seed, epoch, point_base, m_begin, m_end, flags & DPI_BOTH, false, nullptr,
-                      ws, ws_bytes, &w, &a, &r);
+  int rc = label_args(c, &w, &a, &r);
   if (rc || n == 0) return rc;
   if (!stages_prepare(p, net)) return 0;  // nothing to stage: the fused path kernels do it all
-  {
-    std::lock_guard<std::mutex> g(g_prep_mu);
-    prep_tags()[ws] =
-        PrepTag{p, net, tx, n, M, K, m_begin, m_end, flags & DPI_BOTH, pis_x3(net) ? 1 : 0, seed, epoch, point_base, ws_bytes};
-  }
+  prep_tag_set(c);
   if (net->d.kind == 1) {  // GBM: phase 1's noise sums, one wave per SIMD beside the previous path launch
-    char* b = (char*)ws;
-    hipStream_t st = (hipStream_t)stream;
-    int* nq = (int*)(b + w.nq);
-    HIPCHK(hipMemsetAsync(nq, 0, 256 + (size_t)PIS_CLAIM_SLOTS * 4, st));
-    a.noise = (const float*)(b + w.noise);
+    int* nq = (int*)(c.base() + w.nq);
+    HIPCHK(hipMemsetAsync(nq, 0, 256 + (size_t)PIS_CLAIM_SLOTS * 4, c.st()));
+    a.noise = (const float*)(c.base() + w.noise);
     const int nb = (p->e.nx + 3) / 4;
-    hipLaunchKernelGGL(k_noise_shared<DPI_NOISE_SHARED_UNR>, dim3(4 * cu_count() * 3), dim3(P), 0, st, a, nb,
+    hipLaunchKernelGGL(k_noise_shared<DPI_NOISE_SHARED_UNR>, dim3(4 * cu_count() * 3), dim3(P), 0, c.st(), a, nb,
                        n * a.nbp * 8, nq, nq + 64, 1);
     HIPCHK(hipGetLastError());
     return 0;
   }
-  return pis_paths(p, net, tx, n, K, a, w, (char*)ws, (hipStream_t)stream, false, true);
+  return pis_paths(c, a, w);
 }
 
-static int check_prepared(dpi_problem p, dpi_net net, const float* tx, int n, int M, int K, uint64_t seed,
-                          uint32_t epoch, uint32_t point_base, int m_begin, int m_end, int flags, void* ws,
-                          size_t ws_bytes) {
-  if (!(flags & DPI_PREPARED)) {
-    // an unprepared call restages this workspace: a tag left from an unconsumed prepare no longer
-    // describes its rows
-    std::lock_guard<std::mutex> g(g_prep_mu);
-    prep_tags().erase(ws);
-    return 0;
-  }
-  if (n == 0 || !p || !net || !stages_prepare(p, net)) return 0;
-  const PrepTag want{p, net, tx, n, M, K, m_begin, m_end, flags & DPI_BOTH, pis_x3(net) ? 1 : 0, seed, epoch, point_base,
-                     ws_bytes};
-  std::lock_guard<std::mutex> g(g_prep_mu);
-  auto it = prep_tags().find(ws);
-  if (it == prep_tags().end())
-    return fail(DPI_ERR_ARG, "label_moments: DPI_PREPARED without a dpi_label_prepare on this workspace");
-  const bool same = it->second == want;
-  prep_tags().erase(it);
-  if (!same)
+// The prepared call's side of the DPI_PREPARED contract (PrepTag), ahead of the call's own checks.
+static int check_prepared(const LabelCall& c) {
+  // every label call takes the workspace's record: an unprepared one restages the workspace, so a
+  // record left from an unconsumed prepare no longer describes its rows
+  if (!(c.flags & DPI_PREPARED)) return prep_tag_take(c.ws), 0;
+  if (c.n == 0 || !c.p || !c.net || !stages_prepare(c.p, c.net)) return 0;
+  const std::optional<PrepTag> staged = prep_tag_take(c.ws);
+  if (!staged) return fail(DPI_ERR_ARG, "label_moments: DPI_PREPARED without a dpi_label_prepare on this workspace");
+  if (!(*staged == prep_tag(c)))
     return fail(DPI_ERR_ARG, "label_moments: DPI_PREPARED arguments differ from the dpi_label_prepare call on this "
                              "workspace (points, counters, MC range, flags, GEMM precision or workspace size)");
   return 0;
@@ -1442,20 +1441,22 @@ static int check_prepared(dpi_problem p, dpi_net net, const float* tx, int n, in
 int dpi_label_moments(dpi_problem p, dpi_net net, const float* tx, int n, int M, int K, uint64_t seed, uint32_t epoch,
                       uint32_t point_base, int m_begin, int m_end, int flags, float* moments, void* ws,
                       size_t ws_bytes, void* stream) {
-  int rc = check_prepared(p, net, tx, n, M, K, seed, epoch, point_base, m_begin, m_end, flags, ws, ws_bytes);
-  if (rc) return rc;
-  return moments_impl(p, net, tx, n, M, K, seed, epoch, point_base, m_begin, m_end, flags, moments, ws, ws_bytes,
-                      stream, nullptr, 0.f);
+  const LabelCall c{.p = p, .net = net, .tx = tx, .n = n, .M = M, .K = K, .seed = seed, .epoch = epoch,
+                    .point_base = point_base, .m_begin = m_begin, .m_end = m_end, .flags = flags, .ws = ws,
+                    .ws_bytes = ws_bytes, .stream = stream, .moments = moments};
+  int rc = check_prepared(c);
+  return rc ? rc : moments_impl(c);
 }
 
 int dpi_label_moments_finalize(dpi_problem p, dpi_net net, const float* tx, int n, int M, int K, uint64_t seed,
                                uint32_t epoch, uint32_t point_base, int flags, float sample_bound, float* y,
                                float* moments, void* ws, size_t ws_bytes, void* stream) {
   if (n > 0 && !y) return fail(DPI_ERR_ARG, "label_moments_finalize: null y");
-  int rc = check_prepared(p, net, tx, n, M, K, seed, epoch, point_base, 0, M, flags, ws, ws_bytes);
-  if (rc) return rc;
-  return moments_impl(p, net, tx, n, M, K, seed, epoch, point_base, 0, M, flags, moments, ws, ws_bytes, stream, y,
-                      sample_bound);
+  const LabelCall c{.p = p, .net = net, .tx = tx, .n = n, .M = M, .K = K, .seed = seed, .epoch = epoch,
+                    .point_base = point_base, .m_begin = 0, .m_end = M, .flags = flags, .ws = ws,
+                    .ws_bytes = ws_bytes, .stream = stream, .moments = moments, .y = y, .bound = sample_bound};
+  int rc = check_prepared(c);
+  return rc ? rc : moments_impl(c);
 }
 
 int dpi_moments_reduce(float* parts, int n_parts, int n, int nx, float* out, void* stream) {
@@ -1499,15 +1500,16 @@ int dpi_generate_with_gradients(dpi_problem p, dpi_net net, const float* tx, int
   if (rc) return rc;
   if (n < 0 || M < 1 || K < 1) return fail(DPI_ERR_ARG, "generate_with_gradients: bad arguments (n >= 0, M, K >= 1)");
   if (n == 0) return 0;
-  const int F = 1 + p->e.nx;
-  const WsLayout w = ws_layout(net, n, M, F, false, r.park);
+  const WsLayout w = ws_layout(net, n, M, 1 + p->e.nx, {.park = r.park});
   if (!ws || ws_bytes < w.total) return fail(DPI_ERR_WORKSPACE, "workspace too small");
   if (!moments) return fail(DPI_ERR_ARG, "generate_with_gradients: moments buffer (n*2*(1+nx) floats) required");
   if ((rc = dpi_point_baseline(p, net, tx, n, ws, ws_bytes, stream))) return rc;
   if (!y) return fail(DPI_ERR_ARG, "generate_with_gradients: null y");
   // moments and labels come out of the same block-reduce launch
-  return moments_impl(p, net, tx, n, M, K, seed, epoch, point_base, 0, M, flags, moments, ws, ws_bytes, stream, y,
-                      sample_bound);
+  return moments_impl(LabelCall{.p = p, .net = net, .tx = tx, .n = n, .M = M, .K = K, .seed = seed, .epoch = epoch,
+                                .point_base = point_base, .m_begin = 0, .m_end = M, .flags = flags, .ws = ws,
+                                .ws_bytes = ws_bytes, .stream = stream, .moments = moments, .y = y,
+                                .bound = sample_bound});
 }
 
 // ---- Malliavin Hessian labels (generate_with_gradients_and_hessians)
@@ -1518,25 +1520,22 @@ static int hess_tiles(int nx) {
 // [packed block sums n x nbp x TC | moments]
 static size_t hess_extra(int n, int M, int nx, size_t* moff) {
   const int nbp = (M + P - 1) / P;
-  *moff = al256((size_t)n * nbp * hess_tiles(nx) * 256 * 4);
-  return *moff + al256((size_t)n * 2 * (1 + nx) * 4);
+  const size_t sums = al256((size_t)n * nbp * hess_tiles(nx) * 256 * 4);
+  if (moff) *moff = sums;
+  return sums + al256((size_t)n * 2 * (1 + nx) * 4);
 }
 
 size_t dpi_workspace_bytes_hessians(dpi_problem p, dpi_net net, int n, int M) {
   if (!p || n < 0 || M < 0) return 0;
-  size_t moff;
-  return al256(ws_layout(net, n, M, 1 + p->e.nx).total) + hess_extra(n, M, p->e.nx, &moff);
+  return al256(ws_layout(net, n, M, 1 + p->e.nx, {}).total) + hess_extra(n, M, p->e.nx);
 }
 // the same with the GBM noise staging region (dpi_label_prepare + a DPI_PREPARED Hessian-label call)
 size_t dpi_workspace_bytes_hessians_prepared(dpi_problem p, dpi_net net, int n, int M) {
   if (!p || n < 0 || M < 0) return 0;
-  size_t moff;
-  return al256(ws_layout(net, n, M, 1 + p->e.nx, gbm_noise_prep(p, net)).total) + hess_extra(n, M, p->e.nx, &moff);
+  return al256(ws_layout(net, n, M, 1 + p->e.nx, {.noise = gbm_noise_prep(p, net)}).total) + hess_extra(n, M, p->e.nx);
 }
 
-static int hess_moments_impl(dpi_problem p, dpi_net net, const float* tx, int n, int M, int K, uint64_t seed,
-                             uint32_t epoch, uint32_t point_base, int m_begin, int m_end, int flags, float* moments,
-                             float* hsum, void* ws, size_t ws_bytes, void* stream, float* y, float bound) {
+static int hess_moments_impl(const LabelCall& c) {
   // The shared validation and PathArgs fill; a.split selects the fp16-split tangent sweeps
   // (mlp_hdiag_split) unless DPI_GEMM_F32.  label_args also sets a.order (DPI_ORDER) and a.td_dt,
   // which the Hessian-label launch ignores: k_paths reads a.order only in its non-GBM instances (the
@@ -1545,30 +1544,26 @@ static int hess_moments_impl(dpi_problem p, dpi_net net, const float* tx, int n,
   WsLayout w;
   PathArgs a;
   Route r;
-  int rc = label_args(p, net, tx, n, M, K, seed, epoch, point_base, m_begin, m_end, flags, true, moments, ws, ws_bytes,
-                      &w, &a, &r, ROUTE_HESS);
-  if (rc || n == 0) return rc;
-  const int nx = p->e.nx, F = 1 + nx, C = nx * nx, nbp = a.nbp;
-  char* b = (char*)ws;
+  int rc = label_args(c, &w, &a, &r);
+  if (rc || c.n == 0) return rc;
+  const int n = c.n, nx = c.p->e.nx, nbp = a.nbp;
   // a prepared call (GBM): the terminal / integral noise sums were staged by dpi_label_prepare's
   // k_noise_shared in the prepared layout's noise region — the same counters and summation order as
   // the path launch's own rollout, so the labels are bitwise the unprepared call's
-  if ((flags & DPI_PREPARED) && gbm_noise_prep(p, net)) a.noise = (const float*)(b + w.noise);
-  a.c3h1 = DPI_TAG_HTERM | (epoch << 8);
-  a.c3h2 = DPI_TAG_HINT | (epoch << 8);
-  a.hpart = (float*)(b + al256(w.total));  // [packed block sums | moments] behind the layout (hess_extra)
+  if (c.noise()) a.noise = (const float*)(c.base() + w.noise);
+  a.c3h1 = DPI_TAG_HTERM | (c.epoch << 8);
+  a.c3h2 = DPI_TAG_HINT | (c.epoch << 8);
+  a.hpart = (float*)(c.base() + al256(w.total));  // [packed block sums | moments] behind the layout (hess_extra)
   const int NT = (nx + 15) / 16;
-  hipStream_t st = (hipStream_t)stream;
-  Launch q = path_launch(r, a, n * nbp, ws, w, st);
+  Launch q = path_launch(r, a, n * nbp, c, w);
   q.hess = true;
   take_timer(q.t0, q.t1);
-  if ((rc = launch_unit(p, net, q))) return rc;
+  if ((rc = launch_unit(c.p, c.net, q))) return rc;
   HIPCHK(hipGetLastError());
-  hipLaunchKernelGGL(k_reduce, dim3(n, (2 * F + 3) / 4), dim3(256), 0, st, a.partial, n, F, nbp, moments, a.gx,
-                     1.0f / (float)M, (flags & DPI_TERMINAL) ? 1 : 0, bound, y, F + C, net_status(net));
+  launch_reduce(c, a);
   const int bpp = hess_tiles(nx);  // 256 packed words per workgroup: one 16 x 16 tile
-  hipLaunchKernelGGL(k_reduce_hess, dim3((unsigned)((n + 7) / 8) * 8 * bpp), dim3(256), 0, st, a.hpart, n, nx, NT, nbp,
-                     bpp, hsum, 1.0f / (float)M, bound, y, F + C, F, net_status(net));
+  hipLaunchKernelGGL(k_reduce_hess, dim3((unsigned)((n + 7) / 8) * 8 * bpp), dim3(256), 0, c.st(), a.hpart, n, nx, NT,
+                     nbp, bpp, c.hessian_sums, 1.0f / (float)c.M, c.bound, c.y, c.ystride(), 1 + nx, net_status(c.net));
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -1577,10 +1572,12 @@ int dpi_label_moments_hessians(dpi_problem p, dpi_net net, const float* tx, int 
                                uint32_t epoch, uint32_t point_base, int m_begin, int m_end, int flags, float* moments,
                                float* hessian_sums, void* ws, size_t ws_bytes, void* stream) {
   if (!hessian_sums) return fail(DPI_ERR_ARG, "label_moments_hessians: null hessian_sums");
-  int rc = check_prepared(p, net, tx, n, M, K, seed, epoch, point_base, m_begin, m_end, flags, ws, ws_bytes);
-  if (rc) return rc;
-  return hess_moments_impl(p, net, tx, n, M, K, seed, epoch, point_base, m_begin, m_end, flags, moments, hessian_sums,
-                           ws, ws_bytes, stream, nullptr, 0.f);
+  const LabelCall c{.p = p, .net = net, .tx = tx, .n = n, .M = M, .K = K, .seed = seed, .epoch = epoch,
+                    .point_base = point_base, .m_begin = m_begin, .m_end = m_end, .flags = flags, .ws = ws,
+                    .ws_bytes = ws_bytes, .stream = stream, .moments = moments, .hessian_sums = hessian_sums,
+                    .call = ROUTE_HESS};
+  int rc = check_prepared(c);
+  return rc ? rc : hess_moments_impl(c);
 }
 
 int dpi_label_finalize_hessians(dpi_problem p, const float* moments, const float* hessian_sums, int n, int M, int flags,
@@ -1615,12 +1612,14 @@ int dpi_generate_with_gradients_and_hessians(dpi_problem p, dpi_net net, const f
   if (n == 0) return 0;
   if (p->e.kind != DPI_EQ_GBM) return fail(DPI_ERR_UNSUPPORTED, ROUTE_HESS_EQ);
   if ((rc = dpi_point_baseline(p, net, tx, n, ws, ws_bytes, stream))) return rc;
-  const WsLayout w = ws_layout(net, n, M, 1 + p->e.nx);
+  const WsLayout w = ws_layout(net, n, M, 1 + p->e.nx, {});
   size_t moff;
   hess_extra(n, M, p->e.nx, &moff);
   float* moments = (float*)((char*)ws + al256(w.total) + moff);
-  return hess_moments_impl(p, net, tx, n, M, K, seed, epoch, point_base, 0, M, DPI_BOTH, moments, nullptr, ws, ws_bytes,
-                           stream, y, sample_bound);
+  return hess_moments_impl(LabelCall{.p = p, .net = net, .tx = tx, .n = n, .M = M, .K = K, .seed = seed, .epoch = epoch,
+                                     .point_base = point_base, .m_begin = 0, .m_end = M, .flags = DPI_BOTH, .ws = ws,
+                                     .ws_bytes = ws_bytes, .stream = stream, .moments = moments, .y = y,
+                                     .bound = sample_bound, .call = ROUTE_HESS});
 }
 
 }  // extern "C"

@@ -52,7 +52,7 @@ struct NetPisDev {
   // k_gemm_x3 weight scales 2^-s (each split matrix is stored prescaled by 2^s), times the operand
   // exponents of the stored inputs (2^-e) and, for the VJP products, of the output (2^e)
   float te0W, te2W, sn0W, snW[4], nnW[5], nnTW[5], gxnoW;
-  // operand exponents (dpi_kernels.hip x3_exponent): the store scale 2^e of every split operand the
+  // operand exponents (dpi_net_image.h x3_exponent): the store scale 2^e of every split operand the
   // network's products read — k_pis_time's t_encoder hidden layer (xs_te), its output, IN[:, 0:64]
   // (xs_temb), the operand of smooth_net block j (xs_sn[j]); nn_module's A_l (nnO[l]; read back by
   // elu' as nnA[l] = 2^-e).  X (IN[:, 64:]) and GX / NO are stored unscaled.

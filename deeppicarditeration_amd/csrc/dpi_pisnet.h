@@ -206,7 +206,7 @@ __device__ __forceinline__ void pn_st(__amdgpu_buffer_rsrc_t r, int vo, int so, 
 }
 
 // R rows from rows (stride L.stride); grid = ceil(R / 64) blocks.  NTM: the non-temporal hints
-// (DPI_PIS_NT: 2 = loads only, the default; 1 = loads and stores; 0 = none).  At most 232 registers per wave (VGPRs + AGPRs; the
+// above (the host launches NTM = 1, loads only).  At most 232 registers per wave (VGPRs + AGPRs; the
 // 160 KB of LDS leave none for another block): a one-wave k_pis_rollout_shared block of the next
 // batch (<= 48 VGPRs, no LDS) fits on every SIMD beside the two k_pis_net waves (2 x 232 + 48 =
 // 512).  (On gfx950 amdgpu_num_vgpr(N) caps the unified VGPR + AGPR file at 2 N: 116 -> 232; at 224

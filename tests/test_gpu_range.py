@@ -269,7 +269,7 @@ def test_range_group_fp32_overflow_raises():
 # Networks scaled DOWN: every parameter x 1/16 and x 1/256 ("wsd"), and rescaled so every hidden
 # activation is ~1/256 as large while the function stays about the same ("homog": first layer x s,
 # the other hidden biases x s, output weights x 1/s).  The split storage keeps each operand at a
-# calibrated power-of-two scale (dpi_kernels.hip x3_exponent), so its labels must stay fp32-class:
+# calibrated power-of-two scale (dpi_net_image.h x3_exponent), so its labels must stay fp32-class:
 # within 10x of the exact-fp32 mode's rel-L2 on the same inputs (or 2e-7, the labels' own fp32
 # rounding, whichever is larger), and within the 1e-4 bar.
 SMALL = ["ou_pis32_wsd16_K2", "ou_pis32_wsd256_K2", "ou_pis32_homog256_K2", "gbm_mlp16_sdgd_wsd16_K2",

@@ -54,6 +54,9 @@ def main(parent, head, summary=None):
     key = lambda recs: sorted((r["mangled"], sorted(r.items())) for r in recs)  # noqa: E731
     ra, rb = key(build.kernel_resources(parent)), key(build.kernel_resources(head))
     lines.append(f"kernel_resources records: parent {len(ra)}, head {len(rb)}, equal: {ra == rb}")
+    shared = {m for m, _ in ra} & {m for m, _ in rb}  # where one build drops or adds kernels
+    lines.append(f"kernel_resources records of the {len(shared)} shared kernels equal: "
+                 f"{[r for r in ra if r[0] in shared] == [r for r in rb if r[0] in shared]}")
     same = set(a) == set(b) and not differ and ra == rb
     lines.append("IDENTICAL" if same else "DIFFERENT")
     text = "\n".join(lines) + "\n"

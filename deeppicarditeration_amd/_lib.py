@@ -117,6 +117,14 @@ SIGNATURES = {
     "dpi_fit_core_layers_backward": (c_int, [c_int, c_int, P(c_int), P(c_void_p), P(c_void_p), P(c_void_p),
                                              P(c_void_p), c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_size_t,
                                              c_void_p]),
+    "dpi_fit_shell_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "dpi_fit_shell_forward": (c_int, [c_void_p, c_double, c_int, c_int, c_void_p, P(c_void_p), c_void_p, c_int, c_int,
+                                      c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "dpi_fit_shell_loss": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
+                                   c_int, c_int, c_float, c_int, c_float, c_float, c_void_p, c_void_p, c_void_p,
+                                   c_void_p, c_void_p, c_size_t, c_void_p]),
+    "dpi_fit_shell_backward": (c_int, [c_int, c_int, P(c_void_p), P(c_void_p), c_void_p, c_void_p, c_int, c_void_p,
+                                       c_size_t, c_void_p]),
 }
 
 _lib = None

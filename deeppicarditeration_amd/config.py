@@ -6,7 +6,8 @@ POINTS_PER_CALL; TRAIN.BACKEND ("torch": the fit's objectives in PyTorch-ROCm; "
 parameter gradients in the kernels of csrc/dpi_fit.h); TRAIN.FUSED_STEP (false; true, under TRAIN.BACKEND:
 hip: the Adam / AdamW update of every parameter in the launch that forms its gradient, fit.device_step);
 TRAIN.CORE_FORM ("tiles"; "layers", under TRAIN.BACKEND: hip: a PISGradNet's core as one launch per layer and
-pass over the whole GPU, csrc/dpi_fit_layers.h).
+pass over the whole GPU, csrc/dpi_fit_layers.h); TRAIN.PIS_SHELL ("torch"; "hip", under TRAIN.BACKEND: hip: a
+PISGradNet's time networks, g0 part and loss in the kernels of csrc/dpi_fit_shell.h too).
 """
 import ast
 import copy
@@ -123,7 +124,7 @@ def get_default_cfg() -> CfgNode:
     C.TRAIN = _N({"BATCH_SIZE": 2048, "N_EPOCHS": 1, "SUPERVISE_GRADIENT": None, "SUPERVISE_HESSIAN": None,
                   "NUM_HESS_SAMPLES": -1,
                   # this build
-                  "BACKEND": "torch", "FUSED_STEP": False, "CORE_FORM": "tiles"})
+                  "BACKEND": "torch", "FUSED_STEP": False, "CORE_FORM": "tiles", "PIS_SHELL": "torch"})
     C.TRAIN.LOSS = _N({"beta": 0.0, "use_aux_loss": False, "weight_aux_loss": 0.1})
     C.TRAIN.LOSS.SCALER = _N({"cls": None})
     C.TRAIN.LOSS.SCALER.kwargs = _N(new_allowed=True)
@@ -190,6 +191,20 @@ def check_core_form(cfg):
                                   "are the HIP fit's (TRAIN.BACKEND: hip)")
 
 
+PIS_SHELLS = ("torch", "hip")
+
+
+def check_pis_shell(cfg):
+    """TRAIN.PIS_SHELL, what computes a PISGradNet's objective around its core (fit.device_objective), checked when
+    the configuration is loaded; the network is checked at the first batch."""
+    shell = cfg.TRAIN.PIS_SHELL
+    if shell not in PIS_SHELLS:
+        raise ValueError(f"TRAIN.PIS_SHELL {shell!r}: one of {PIS_SHELLS}")
+    if shell != "torch" and cfg.TRAIN.BACKEND != "hip":
+        raise NotImplementedError(f"TRAIN.PIS_SHELL: {shell} with TRAIN.BACKEND: {cfg.TRAIN.BACKEND}: the shell kernels "
+                                  "are the HIP fit's (TRAIN.BACKEND: hip)")
+
+
 def _read_file_only(path):
     with open(path) as f:
         return CfgNode(yaml.safe_load(f) or {}, new_allowed=True)
@@ -230,5 +245,6 @@ def load_cfg(cfg_file: str, override: List[str] = None) -> CfgNode:
         raise ValueError(f"TRAIN.BACKEND {cfg.TRAIN.BACKEND!r}: one of 'torch', 'hip'")
     check_fused_step(cfg)
     check_core_form(cfg)
+    check_pis_shell(cfg)
     cfg.freeze()
     return cfg

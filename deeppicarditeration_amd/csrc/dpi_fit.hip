@@ -1,7 +1,8 @@
 // C ABI of the fit's device path (include/dpi.h: dpi_fit_workspace_bytes, dpi_fit_gradients, dpi_fit_step for
 // construct_mlp value networks; dpi_fit_core_workspace_bytes, dpi_fit_core_forward, dpi_fit_core_backward
-// for PISGradNet's nn_module, and its layer-wise form dpi_fit_core_layers_*); the kernels are in dpi_fit.h and
-// dpi_fit_layers.h.  Not a row of the unit table: nothing here depends on a (problem, network) route.
+// for PISGradNet's nn_module, its layer-wise form dpi_fit_core_layers_*, and dpi_fit_shell_* for what surrounds
+// it: the time networks, the g0 part and the loss); the kernels are in dpi_fit.h, dpi_fit_layers.h and
+// dpi_fit_shell.h.  Not a row of the unit table: nothing here depends on a (problem, network) route.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -10,7 +11,11 @@
 
 #include "dpi_fit.h"
 #include "dpi_fit_layers.h"
+#include "dpi_fit_shell.h"
 #include "dpi_host.h"
+
+// the device functor of a problem handle (dpi_kernels.hip, which owns the handle's struct)
+extern "C" DPI_HIDDEN const dpi::EqDev* problem_eq(dpi_problem p);
 
 namespace {
 
@@ -418,6 +423,227 @@ extern "C" int dpi_fit_step(int n_in, int n_hidden, const int* widths, int act, 
   launch_fit_rows(s.f, act, st);
   HIPCHK(hipGetLastError());
   hipLaunchKernelGGL(k_fit_wgrad_step, dim3(blk + 1), dim3(256), 0, st, s);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+// ---- the PISGradNet shell (dpi_fit_shell_*)
+
+namespace {
+
+int shell_shape(const std::string& who, int nx, int n_smooth_hidden, int B) {
+  if (nx < 1 || n_smooth_hidden < 1) return fail(DPI_ERR_ARG, who + ": bad shape (nx >= 1, n_smooth_hidden >= 1)");
+  if (nx > SH_NX_MAX)
+    return fail(DPI_ERR_UNSUPPORTED, who + ": nx = " + std::to_string(nx) + " > 128, PISGradNet's state dimensions");
+  if (n_smooth_hidden > SH_LMAX)
+    return fail(DPI_ERR_UNSUPPORTED, who + ": smooth_net depth " + std::to_string(n_smooth_hidden) + " > 4 (the 64 -> 64 "
+                                     "layers, len(NETWORK.NEURONS))");
+  if (B < 1) return fail(DPI_ERR_ARG, who + ": B = " + std::to_string(B) + " < 1 row (the loss is a mean over the batch)");
+  if (B > (1 << 24)) return fail(DPI_ERR_UNSUPPORTED, who + ": B > 2^24 rows in one batch");
+  return 0;
+}
+
+// the workspace layout of the shell: the tiles' loss sums (doubles) first, then the [unit][row] arrays over
+// 64 (tiles + 1) rows; fills the offsets (L, nx, tiles set) and returns the float count
+size_t shell_layout(FitShellArgs& a) {
+  const size_t R = (size_t)(a.tiles + 1) * FIT_ROWS;
+  size_t o = 2 * (size_t)a.tiles * (1 + a.nx);
+  auto take = [&](int units) { const size_t at = o; o += (size_t)units * R; return at; };
+  a.offE = take(SH_NE);
+  a.offAt = take(SH_NT);
+  a.offPt = take(SH_NT);
+  a.offZt[0] = take(SH_NT);
+  a.offZt[1] = take(SH_NT);
+  for (int k = 0; k <= a.L; ++k) {
+    a.offAs[k] = take(SH_NT);
+    a.offPs[k] = take(SH_NT);
+    a.offZs[k] = take(SH_NT);
+  }
+  a.offZL = take(1);
+  a.offDW = take(SH_NT);
+  return o;
+}
+
+void shell_dims(FitShellArgs& a, int nx, int n_smooth_hidden, int B) {
+  a.L = n_smooth_hidden;
+  a.nx = nx;
+  a.B = B;
+  a.tiles = (B + FIT_ROWS - 1) / FIT_ROWS;
+  a.nt = SH_NT;
+  a.ne = SH_NE;
+}
+
+int shell_workspace(const std::string& who, size_t need, const void* ws, size_t ws_bytes) {
+  if ((uintptr_t)ws % 8) return fail(DPI_ERR_ARG, who + ": the workspace must be 8-byte aligned");
+  if (!ws || ws_bytes < need)
+    return fail(DPI_ERR_WORKSPACE, who + ": workspace too small (" + std::to_string(ws_bytes) + " < " +
+                                   std::to_string(need) + " bytes, dpi_fit_shell_workspace_bytes)");
+  return 0;
+}
+
+// the time networks' table in state-dict order: timestep_phase, t_encoder's (W, b) x 2, smooth_net's (W, b) x (L + 2)
+int shell_table_size(int L) { return 5 + 2 * (L + 2); }
+
+int shell_params(FitShellArgs& a, const std::string& who, const float* const* params) {
+  if (!params) return fail(DPI_ERR_ARG, who + ": null pointer table (params)");
+  for (int k = 0; k < shell_table_size(a.L); ++k)
+    if (!params[k]) return fail(DPI_ERR_ARG, who + ": null entry " + std::to_string(k) + " in the parameter table");
+  a.phase = params[0];
+  for (int k = 0; k < 2; ++k) {
+    a.Wt[k] = params[1 + 2 * k];
+    a.bt[k] = params[2 + 2 * k];
+  }
+  for (int k = 0; k <= a.L + 1; ++k) {
+    a.Ws[k] = params[5 + 2 * k];
+    a.bs[k] = params[6 + 2 * k];
+  }
+  return 0;
+}
+
+}  // namespace
+
+extern "C" size_t dpi_fit_shell_workspace_bytes(int nx, int n_smooth_hidden, int B) {
+  if (shell_shape("fit_shell_workspace_bytes", nx, n_smooth_hidden, B)) return 0;
+  FitShellArgs a{};
+  shell_dims(a, nx, n_smooth_hidden, B);
+  return shell_layout(a) * sizeof(float);
+}
+
+extern "C" int dpi_fit_shell_forward(dpi_problem p, double T, int nx, int n_smooth_hidden, const float* coeff,
+                                     const float* const* params, const float* tx, int tx_stride, int B, int grad,
+                                     float* tau, float* s, float* res, float* res_x, void* ws, size_t ws_bytes,
+                                     void* stream) {
+  const std::string who = "fit_shell_forward";
+  int rc = shell_shape(who, nx, n_smooth_hidden, B);
+  if (rc) return rc;
+  if (!std::isfinite(T)) return fail(DPI_ERR_ARG, who + ": T must be finite");
+  if (tx_stride < 1 + nx) return fail(DPI_ERR_ARG, who + ": tx row stride < 1 + nx");
+  FitShellArgs a{};
+  shell_dims(a, nx, n_smooth_hidden, B);
+  if ((rc = shell_params(a, who, params))) return rc;
+  if (!coeff || !tx || !tau || !s || !res || (grad && !res_x))
+    return fail(DPI_ERR_ARG, who + ": null coeff, tx, tau, s, res or (with grad) res_x");
+  if ((rc = shell_workspace(who, shell_layout(a) * sizeof(float), ws, ws_bytes))) return rc;
+  const EqDev* eq = problem_eq(p);
+  if (!eq) return fail(DPI_ERR_ARG, who + ": null problem");
+  if (eq->kind != DPI_EQ_OU)
+    return fail(DPI_ERR_UNSUPPORTED, who + ": the problem is not an OU problem (dpi_problem_create_ou): g0 and its "
+                                     "gradient are the OU mixture's closed forms");
+  if (eq->ncomp < 1 || eq->ncomp > NSG)
+    return fail(DPI_ERR_UNSUPPORTED, who + ": " + std::to_string(eq->ncomp) + " mixture components > 8 (NSG)");
+  if (eq->nx != nx)
+    return fail(DPI_ERR_ARG, who + ": the problem has nx = " + std::to_string(eq->nx) + ", the call " + std::to_string(nx));
+  a.eq = *eq;
+  a.T = T;
+  a.coeff = coeff;
+  a.tx = tx;
+  a.txstride = tx_stride;
+  a.grad = grad ? 1 : 0;
+  a.tau = tau;
+  a.s = s;
+  a.res = res;
+  a.res_x = res_x;
+  a.ws = (float*)ws;
+  hipLaunchKernelGGL(k_fit_shell_fwd, dim3(a.tiles + 1), dim3(FIT_NTH), 0, (hipStream_t)stream, a);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+extern "C" int dpi_fit_shell_loss(int nx, const float* sp, const float* q, const float* s, const float* res,
+                                  const float* res_x, const float* tx, int tx_stride, const float* y, int y_stride,
+                                  int B, float beta, int loss_kind, float clip, float kappa, float* losses, float* e,
+                                  float* r, float* sbar, void* ws, size_t ws_bytes, void* stream) {
+  const std::string who = "fit_shell_loss";
+  int rc = shell_shape(who, nx, 1, B);
+  if (rc) return rc;
+  if (loss_kind != DPI_FIT_LOSS_SQUARE && loss_kind != DPI_FIT_LOSS_CLIP)
+    return fail(DPI_ERR_ARG, who + ": loss kind (DPI_FIT_LOSS_SQUARE or DPI_FIT_LOSS_CLIP)");
+  if (loss_kind == DPI_FIT_LOSS_CLIP && !(clip > 0.f && std::isfinite(clip)))
+    return fail(DPI_ERR_ARG, who + ": clip must be positive and finite");
+  if (!std::isfinite(beta) || !(kappa >= 0.f) || !std::isfinite(kappa))
+    return fail(DPI_ERR_ARG, who + ": beta must be finite and the gradient weight kappa >= 0 and finite");
+  if (tx_stride < 1 + nx || y_stride < 1 + nx) return fail(DPI_ERR_ARG, who + ": row stride of tx or y < 1 + nx");
+  const bool grad = kappa > 1e-9f && q;  // build_objective's threshold for the plain value fit
+  if (!sp || !s || !res || !tx || !y || !losses || !e || !sbar)
+    return fail(DPI_ERR_ARG, who + ": null sp, s, res, tx, y, losses, e or sbar");
+  if (grad && (!res_x || !r)) return fail(DPI_ERR_ARG, who + ": null res_x or r with q given and kappa > 1e-9");
+  FitShellLossArgs a{};
+  a.nx = nx;
+  a.B = B;
+  a.tiles = (B + FIT_ROWS - 1) / FIT_ROWS;
+  if ((rc = shell_workspace(who, (size_t)a.tiles * (1 + nx) * sizeof(double), ws, ws_bytes))) return rc;
+  a.sp = sp;
+  a.q = q;
+  a.s = s;
+  a.res = res;
+  a.res_x = res_x;
+  a.tx = tx;
+  a.y = y;
+  a.txstride = tx_stride;
+  a.ystride = y_stride;
+  a.grad = grad ? 1 : 0;
+  a.clipped = loss_kind == DPI_FIT_LOSS_CLIP;
+  a.beta = beta;
+  a.clip = clip;
+  a.kappa = kappa;
+  a.losses = losses;
+  a.e = e;
+  a.r = r;
+  a.sbar = sbar;
+  a.part = (double*)ws;
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(k_fit_shell_loss, dim3(a.tiles), dim3(256), 0, st, a);
+  HIPCHK(hipGetLastError());
+  hipLaunchKernelGGL(k_fit_shell_loss_sum, dim3(1), dim3(256), 0, st, a);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+extern "C" int dpi_fit_shell_backward(int nx, int n_smooth_hidden, const float* const* params, float* const* grads,
+                                      const float* dtau, const float* sbar, int B, void* ws, size_t ws_bytes,
+                                      void* stream) {
+  const std::string who = "fit_shell_backward";
+  int rc = shell_shape(who, nx, n_smooth_hidden, B);
+  if (rc) return rc;
+  FitShellArgs a{};
+  shell_dims(a, nx, n_smooth_hidden, B);
+  if ((rc = shell_params(a, who, params))) return rc;
+  if (!grads) return fail(DPI_ERR_ARG, who + ": null pointer table (grads)");
+  for (int k = 0; k < shell_table_size(a.L); ++k)
+    if (!grads[k]) return fail(DPI_ERR_ARG, who + ": null entry " + std::to_string(k) + " in the gradient table");
+  if (!dtau || !sbar) return fail(DPI_ERR_ARG, who + ": null dtau or sbar");
+  if ((rc = shell_workspace(who, shell_layout(a) * sizeof(float), ws, ws_bytes))) return rc;
+  a.dtau = dtau;
+  a.sbar = sbar;
+  a.ws = (float*)ws;
+  const int L = a.L;
+  FitShellWgradArgs w{};
+  w.B = B;
+  w.tiles = a.tiles;
+  int n = 0;
+  auto table = [&](size_t offZ, size_t offA, float* dW, float* db, int nout, int nin, int nz, int zrow, int zero_bias,
+                   bool ones) {
+    w.lay[n] = ShellLayer{ones ? nullptr : a.ws + offZ, a.ws + offA, dW, db, nout, nin, nz, zrow, zero_bias};
+    ++n;
+  };
+  table(a.offZt[0], a.offE, grads[1], grads[2], SH_NT, SH_NE, SH_NT, 0, 0, false);
+  table(a.offZt[1], a.offAt, grads[3], grads[4], SH_NT, SH_NT, SH_NT, 0, 0, false);
+  table(a.offZs[0], a.offE, grads[5], grads[6], SH_NT, SH_NE, SH_NT, 1, 0, false);
+  for (int k = 1; k <= L; ++k)
+    table(a.offZs[k], a.offAs[k - 1], grads[5 + 2 * k], grads[6 + 2 * k], SH_NT, SH_NT, SH_NT, 1, 0, false);
+  table(a.offZL, a.offAs[L], grads[5 + 2 * (L + 1)], grads[6 + 2 * (L + 1)], nx, SH_NT, 1, 1, 1, false);
+  table(0, a.offDW, grads[0], nullptr, 1, SH_NT, 1, 1, 0, true);
+  w.nlay = n;
+  int blk = 0;
+  for (int l = 0; l < n; ++l) {
+    w.blk0[l] = blk;
+    blk += ((w.lay[l].nout + FIT_WT - 1) / FIT_WT) * ((w.lay[l].nin + FIT_WT - 1) / FIT_WT);
+  }
+  w.blk0[n] = blk;
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(k_fit_shell_bwd, dim3(a.tiles + 1), dim3(FIT_NTH), 0, st, a);
+  HIPCHK(hipGetLastError());
+  hipLaunchKernelGGL(k_fit_shell_wgrad, dim3(blk), dim3(256), 0, st, w);
   HIPCHK(hipGetLastError());
   return 0;
 }

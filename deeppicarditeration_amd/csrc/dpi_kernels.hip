@@ -393,6 +393,10 @@ int dpi_problem_destroy(dpi_problem p) {
   return 0;
 }
 
+// The device functor of a problem for the fit's shell entries (dpi_fit.hip, which does not see the handle's
+// struct); NULL for a NULL handle.  Host memory of the handle: valid until dpi_problem_destroy.
+DPI_HIDDEN const dpi::EqDev* problem_eq(dpi_problem p) { return p ? &p->e : nullptr; }
+
 }  // extern "C"
 
 // PISGradNet pipeline rows (floats per path) and chunking.  x3: split-storage regions, every

@@ -4,7 +4,8 @@ loss and the parameter gradients of the value and gradient kinds come from the H
 csrc/dpi_fit.h (`device_objective`, DESIGN.md §5.1): in two launches for a construct_mlp value network;
 for a PISGradNet, nn_module and its double backward in three launches (`_PISCore`) between the time networks
 and the loss, which stay torch's — or, under TRAIN.CORE_FORM: layers, in one launch per layer and pass
-(csrc/dpi_fit_layers.h).  The fit consumes the device-resident labels.
+(csrc/dpi_fit_layers.h); under TRAIN.PIS_SHELL: hip the time networks, the g0 part and the loss come from HIP as
+well (`_PISShell`, csrc/dpi_fit_shell.h).  The fit consumes the device-resident labels.
 
 - `value_objective`: PicardBaseSolution.training_step (picard/solution.py:74-81), the exp(beta t)
   weighted value loss;
@@ -336,6 +337,23 @@ def _check_core_form(core_form):
         raise ValueError(f"TRAIN.CORE_FORM {core_form!r}: one of {tuple(CORE_FORMS)}")
 
 
+# TRAIN.PIS_SHELL: what computes a PISGradNet's objective around the core.  "torch": the time networks and the loss
+# are torch ops under autograd (`_pis_objective`); "hip": the C entries dpi_fit_shell_* (csrc/dpi_fit_shell.h),
+# chained with the core's in `_PISShell`.
+PIS_SHELLS = ("torch", "hip")
+
+
+def _check_pis_shell(pis_shell):
+    if pis_shell not in PIS_SHELLS:
+        raise ValueError(f"TRAIN.PIS_SHELL {pis_shell!r}: one of {PIS_SHELLS}")
+
+
+def _refuse_shell_without_pisgradnet(pis_shell, net):
+    if pis_shell != "torch" and type(net).__name__ != "PISGradNet":
+        raise NotImplementedError(f"TRAIN.PIS_SHELL: {pis_shell} with a {type(net).__name__} network: the shell is a "
+                                  "PISGradNet's (NETWORK.PISGRADNET)")
+
+
 class _PISPlan:
     """What `device_objective` needs of one PISGradNet (this build's class or the reference's of that
     name), checked once and before the library is touched: the closed-form g and g_x behind g0, the
@@ -343,11 +361,13 @@ class _PISPlan:
     and the C-ABI shape arguments.  What the core does not cover is refused by name.  core_form
     (TRAIN.CORE_FORM) names the C entries `_PISCore` calls."""
 
-    def __init__(self, net, nx, core_form="tiles"):
+    def __init__(self, net, nx, core_form="tiles", pis_shell="torch"):
         from . import _lib
         _check_core_form(core_form)
+        _check_pis_shell(pis_shell)
         self.net = net
         self.core_form = core_form
+        self.pis_shell = pis_shell
         self.ws_bytes, self.forward, self.backward = CORE_FORMS[core_form]
         owner = getattr(net.g0, "__self__", None)
         if owner is None or type(owner).__name__ != "OUProcessEquation":
@@ -384,6 +404,37 @@ class _PISPlan:
         self.params = [p for m in lin for p in (m.weight, m.bias)]  # state-dict order
         self.ws = None
         self.calls = 0  # forward calls so far: a backward must find the state of its own forward in ws
+        if pis_shell == "hip":
+            self._shell_table(owner)
+
+    def _shell_table(self, equation):
+        """TRAIN.PIS_SHELL: hip: the time networks' parameters in state-dict order (the table of dpi_fit_shell_*),
+        the timestep_coeff buffer and the equation that hands out the problem handle; the shell has a workspace of
+        its own."""
+        net, nx = self.net, self.nx
+        if not callable(getattr(equation, "dpi_problem", None)):
+            raise NotImplementedError(f"TRAIN.PIS_SHELL: hip with a {type(equation).__name__} that has no dpi_problem(): "
+                                      "the shell kernels take g0 from the compiled problem handle")
+        chains = []
+        for name, seq, dims in (("t_encoder", net.t_encoder, [2 * PIS_CHANNELS, PIS_CHANNELS, PIS_CHANNELS]),
+                                ("smooth_net", net.smooth_net,
+                                 [2 * PIS_CHANNELS] + [PIS_CHANNELS] * (self.n_hidden + 1) + [nx])):
+            mods = list(seq)
+            lin, acts = mods[0::2], mods[1::2]
+            if (len(mods) != 2 * len(dims) - 3 or not all(isinstance(m, torch.nn.Linear) and m.bias is not None
+                                                          for m in lin)
+                    or not all(isinstance(m, torch.nn.ELU) and m.alpha == 1.0 for m in acts)
+                    or [(m.in_features, m.out_features) for m in lin] != list(zip(dims[:-1], dims[1:]))):
+                raise NotImplementedError(f"TRAIN.PIS_SHELL: hip with a PISGradNet whose {name} is not the Linear / ELU "
+                                          f"(alpha = 1) chain {' -> '.join(map(str, dims))} with biases")
+            chains += [p for m in lin for p in (m.weight, m.bias)]
+        coeff = net.timestep_coeff
+        if coeff.dtype != torch.float32 or not coeff.is_contiguous() or coeff.numel() != PIS_CHANNELS:
+            raise NotImplementedError("TRAIN.PIS_SHELL: hip with a timestep_coeff buffer that is not fp32 contiguous of "
+                                      f"{PIS_CHANNELS} entries")
+        self.shell_equation = equation
+        self.shell_params = [net.timestep_phase] + chains
+        self.shell_ws = None
 
     def table(self, tensors):
         from . import _lib
@@ -445,6 +496,90 @@ class _PISCore(torch.autograd.Function):
         return (None, None, dtau, None) + tuple(grads)
 
 
+class _PISShell(torch.autograd.Function):
+    """A PISGradNet's whole objective from the library (TRAIN.PIS_SHELL: hip): losses (2 + nx,) =
+    (total, v_loss, g_loss[nx]) of one batch.  Its forward chains dpi_fit_shell_forward (tau, s, the g0 part), the
+    core's forward of the plan's form (sp, q), dpi_fit_shell_loss (the loss and the seeds e, r, sbar), the core's
+    backward (nn_module's gradients and taubar) and dpi_fit_shell_backward (the time networks' gradients) on
+    torch's current stream, with no host synchronisation; the gradients are kept and handed to the parameters
+    in backward, scaled by the gradient arriving at losses[0], as `_DeviceFit` does.  params: the shell's table,
+    then nn_module's."""
+
+    @staticmethod
+    def forward(ctx, plan, tx, y, beta, loss_kind, clip, kappa, *params):
+        from . import _lib
+        lib = _lib.load()
+        tx, y = tx.detach(), y.detach()
+        if tx.stride(-1) != 1:
+            tx = tx.contiguous()
+        if y.stride(-1) != 1:
+            y = y.contiguous()
+        B, nx, dev = int(tx.shape[0]), plan.nx, tx.device
+        grad = kappa > 1e-9
+        ns = len(plan.shell_params)
+        shell_p, core_p = params[:ns], params[ns:]
+        need = int(lib.dpi_fit_shell_workspace_bytes(nx, plan.n_hidden, B))
+        if plan.shell_ws is None or plan.shell_ws.numel() < need or plan.shell_ws.device != dev:
+            plan.shell_ws = torch.empty(max(need, 8), dtype=torch.uint8, device=dev)
+        need = int(getattr(lib, plan.ws_bytes)(nx, plan.n_hidden, plan.widths, B))
+        if plan.ws is None or plan.ws.numel() < need or plan.ws.device != dev:
+            plan.ws = torch.empty(max(need, 4), dtype=torch.uint8, device=dev)
+        sws, cws = plan.shell_ws, plan.ws
+        st = torch.cuda.current_stream(dev).cuda_stream
+        new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)  # noqa: E731
+        ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        W, b = plan.table(core_p[0::2]), plan.table(core_p[1::2])
+        tau, s, res, sp = new(B, PIS_CHANNELS), new(B), new(B), new(B)
+        res_x, q, r = (new(B, nx), new(B, nx), new(B, nx)) if grad else (None, None, None)
+        _lib.check(lib.dpi_fit_shell_forward(plan.shell_equation.dpi_problem(), float(plan.net.T), nx, plan.n_hidden,
+                                             plan.net.timestep_coeff.data_ptr(), plan.table(shell_p), tx.data_ptr(),
+                                             int(tx.stride(0)), B, int(grad), tau.data_ptr(), s.data_ptr(),
+                                             res.data_ptr(), ptr(res_x), sws.data_ptr(), sws.numel(), st),
+                   "dpi_fit_shell_forward")
+        # x is the columns 1 .. nx of tx, read in place through its row stride
+        _lib.check(getattr(lib, plan.forward)(nx, plan.n_hidden, plan.widths, W, b, tau.data_ptr(), PIS_CHANNELS,
+                                              tx.data_ptr() + tx.element_size(), int(tx.stride(0)), B, sp.data_ptr(),
+                                              ptr(q), cws.data_ptr(), cws.numel(), st), plan.forward)
+        losses, e, sbar = new(2 + nx), new(B), new(B)
+        _lib.check(lib.dpi_fit_shell_loss(nx, sp.data_ptr(), ptr(q), s.data_ptr(), res.data_ptr(), ptr(res_x),
+                                          tx.data_ptr(), int(tx.stride(0)), y.data_ptr(), int(y.stride(0)), B,
+                                          float(beta), loss_kind, float(clip), float(kappa), losses.data_ptr(),
+                                          e.data_ptr(), ptr(r), sbar.data_ptr(), sws.data_ptr(), sws.numel(), st),
+                   "dpi_fit_shell_loss")
+        core_g, shell_g = [torch.empty_like(p) for p in core_p], [torch.empty_like(p) for p in shell_p]
+        dtau = new(B, PIS_CHANNELS)
+        _lib.check(getattr(lib, plan.backward)(nx, plan.n_hidden, plan.widths, W, b, plan.table(core_g[0::2]),
+                                               plan.table(core_g[1::2]), e.data_ptr(), ptr(r), B, dtau.data_ptr(),
+                                               cws.data_ptr(), cws.numel(), st), plan.backward)
+        _lib.check(lib.dpi_fit_shell_backward(nx, plan.n_hidden, plan.table(shell_p), plan.table(shell_g),
+                                              dtau.data_ptr(), sbar.data_ptr(), B, sws.data_ptr(), sws.numel(), st),
+                   "dpi_fit_shell_backward")
+        plan.calls += 1
+        ctx.grads = shell_g + core_g
+        total, parts = losses[:1], losses[1:]
+        ctx.mark_non_differentiable(parts)
+        return total, parts
+
+    @staticmethod
+    def backward(ctx, g_total, _g_parts):
+        return (None,) * 7 + tuple(torch._foreach_mul(ctx.grads, g_total.reshape(())))
+
+
+def _pis_shell_objective(plan, tx, y, beta, loss_kind, clip, kappa, value_only):
+    """`_pis_objective` with the shell in HIP: the same loss shape and `info` keys from `_PISShell`'s losses."""
+    from . import _lib
+    if tx.dtype != torch.float32 or y.dtype != torch.float32:
+        raise NotImplementedError(f"TRAIN.BACKEND: hip with PISGradNet and {tx.dtype} batches: fp32 only "
+                                  "(DATA.FLOAT: float)")
+    if tx.device.type != "cuda":
+        raise _lib.DPIError("TRAIN.BACKEND: hip needs the batch on the GPU (there is no CPU fallback)")
+    total, parts = _PISShell.apply(plan, tx, y, beta, loss_kind, clip, 0.0 if value_only else kappa,
+                                   *plan.shell_params, *plan.params)
+    if value_only:
+        return total, {}
+    return total, {"train_gradient_loss(unscaled)": parts[1:].sum(dim=-1, keepdim=True), "train_value_loss": parts[:1]}
+
+
 def _pis_objective(plan, tx, y, beta, loss_fn, scaler, value_only):
     """`value_objective` / `gradient_objective` on a PISGradNet u = s sp + (1 - s) g0(c x): the time
     networks (t_encoder, smooth_net, the embedding) run in torch with ordinary autograd, the parameter-free
@@ -495,7 +630,7 @@ def _device_loss_args(loss_fn, scaler):
     return loss_kind, clip, c, c <= 1e-9
 
 
-def device_objective(beta, loss_fn, scaler, nx, core_form="tiles"):
+def device_objective(beta, loss_fn, scaler, nx, core_form="tiles", pis_shell="torch"):
     """The device form of `value_objective` (scaler None, or a FixedLossScaler of weight <= 1e-9) and of
     `gradient_objective` with a FixedLossScaler: loss and parameter gradients from the HIP kernels of
     csrc/dpi_fit.h, same signature and `info` keys.  The optimizer stays torch's:
@@ -503,22 +638,30 @@ def device_objective(beta, loss_fn, scaler, nx, core_form="tiles"):
     the first batch: a construct_mlp value network takes `_DeviceFit` (loss and gradients in two launches),
     a PISGradNet takes `_pis_objective` (nn_module in HIP through `_PISCore`, the rest in torch).
     core_form (TRAIN.CORE_FORM): the form of the PISGradNet core, "tiles" or "layers"; "layers" with any other
-    network is refused by name at the first batch, before the library is touched."""
+    network is refused by name at the first batch, before the library is touched.
+    pis_shell (TRAIN.PIS_SHELL): "torch", or "hip": a PISGradNet's whole objective from the library (`_PISShell`:
+    the time networks, the g0 part, the loss and every parameter gradient in HIP, with either form of the core);
+    "hip" with any other network is refused the same way."""
     _check_core_form(core_form)
+    _check_pis_shell(pis_shell)
     loss_kind, clip, c, value_only = _device_loss_args(loss_fn, scaler)
     plans = {}
 
     def objective(net, tx, y):
         plan = plans.get(id(net))
         if plan is None or plan.net is not net:
+            _refuse_shell_without_pisgradnet(pis_shell, net)
             if type(net).__name__ == "PISGradNet":
-                plan = plans[id(net)] = _PISPlan(net, nx, core_form)
+                shell = () if pis_shell == "torch" else (pis_shell,)  # the default reproduces the call as it was
+                plan = plans[id(net)] = _PISPlan(net, nx, core_form, *shell)
             elif core_form != "tiles":
                 raise NotImplementedError(f"TRAIN.CORE_FORM: {core_form} with a {type(net).__name__} network: the "
                                           "forms are the PISGradNet core's (NETWORK.PISGRADNET)")
             else:
                 plan = plans[id(net)] = _DevicePlan(net, nx)
         if isinstance(plan, _PISPlan):
+            if plan.pis_shell == "hip":
+                return _pis_shell_objective(plan, tx, y, beta, loss_kind, clip, c, value_only)
             return _pis_objective(plan, tx, y, beta, loss_fn, scaler, value_only)
         total, parts = _DeviceFit.apply(plan, tx, y, beta, loss_kind, clip, 0.0 if value_only else c, *plan.params)
         if value_only:
@@ -575,7 +718,7 @@ def _fused_state(opt, plan):
     return states
 
 
-def device_step(beta, loss_fn, scaler, nx, core_form="tiles"):
+def device_step(beta, loss_fn, scaler, nx, core_form="tiles", pis_shell="torch"):
     """One whole training step on the device (TRAIN.FUSED_STEP under TRAIN.BACKEND: hip):
     `step(net, opt, tx, y) -> losses (2 + nx,)` = (total, v_loss, g_loss[nx]) of the batch, formed before the
     update, from dpi_fit_step: k_fit_rows and k_fit_wgrad_step compute the loss and the gradients and apply
@@ -586,14 +729,16 @@ def device_step(beta, loss_fn, scaler, nx, core_form="tiles"):
     torch's and a run may switch between the two step forms).  Same options as `device_objective`; an
     optimizer or network the kernel does not cover is refused by name at the first batch, before the library
     is touched.  There is no fallback.  core_form other than "tiles" is refused as `device_objective` refuses
-    it: the fused step has no PISGradNet core."""
+    it: the fused step has no PISGradNet core; so is pis_shell other than "torch"."""
     _check_core_form(core_form)
+    _check_pis_shell(pis_shell)
     loss_kind, clip, c, value_only = _device_loss_args(loss_fn, scaler)
     plans = {}
 
     def step(net, opt, tx, y):
         plan = plans.get(id(net))
         if plan is None or plan.net is not net:
+            _refuse_shell_without_pisgradnet(pis_shell, net)
             if core_form != "tiles" and type(net).__name__ != "PISGradNet":
                 raise NotImplementedError(f"TRAIN.CORE_FORM: {core_form} with a {type(net).__name__} network: the "
                                           "forms are the PISGradNet core's (NETWORK.PISGRADNET)")
@@ -638,7 +783,7 @@ def make_scaler(scaler_cfg):
 
 
 def build_objective(train_cfg, nx, supervise_gradient, supervise_hessian, output_dim=1, backend="torch",
-                    fused_step=False, core_form="tiles"):
+                    fused_step=False, core_form="tiles", pis_shell="torch"):
     """PicardRunner.get_solution (picard_iteration.py:113-118) + the wrappers' construct_solution
     (solution_jac.py:112-119): returns (objective, kind) with kind in {"value", "gradient",
     "gradient_hessian", "head_value_gradient", "head_only_gradient"}.  output_dim: the network's
@@ -648,10 +793,15 @@ def build_objective(train_cfg, nx, supervise_gradient, supervise_hessian, output
     kinds "value" and "gradient" with FixedLossScaler and refuses every other option by name.
     fused_step (TRAIN.FUSED_STEP, "hip" only): what is returned in the objective's place is the `device_step`
     of the same options, for `fused_train_steps`.
-    core_form (TRAIN.CORE_FORM, other than "tiles" under "hip" only): handed to `device_objective`."""
+    core_form (TRAIN.CORE_FORM, other than "tiles" under "hip" only): handed to `device_objective`.
+    pis_shell (TRAIN.PIS_SHELL, "hip" under backend "hip" only): handed on the same way."""
     if backend not in BACKENDS:
         raise ValueError(f"TRAIN.BACKEND {backend!r}: one of {BACKENDS}")
     _check_core_form(core_form)
+    _check_pis_shell(pis_shell)
+    if pis_shell != "torch" and backend != "hip":
+        raise NotImplementedError(f"TRAIN.PIS_SHELL: {pis_shell} with TRAIN.BACKEND: {backend}: the shell kernels are "
+                                  "the HIP fit's (TRAIN.BACKEND: hip)")
     if core_form != "tiles" and backend != "hip":
         raise NotImplementedError(f"TRAIN.CORE_FORM: {core_form} with TRAIN.BACKEND: {backend}: the core's forms are "
                                   "the HIP fit's (TRAIN.BACKEND: hip)")
@@ -660,7 +810,7 @@ def build_objective(train_cfg, nx, supervise_gradient, supervise_hessian, output
                                   "(TRAIN.BACKEND: hip)")
     if backend == "hip":
         return _build_device_objective(train_cfg, nx, supervise_gradient, supervise_hessian, output_dim,
-                                       device_step if fused_step else device_objective, core_form)
+                                       device_step if fused_step else device_objective, core_form, pis_shell)
     loss_cfg = train_cfg["LOSS"]
     beta = float(loss_cfg["beta"])
     loss_fn = make_loss_fn(loss_cfg.get("FN"))
@@ -699,11 +849,13 @@ def build_objective(train_cfg, nx, supervise_gradient, supervise_hessian, output
 
 
 def _build_device_objective(train_cfg, nx, supervise_gradient, supervise_hessian, output_dim, make,
-                            core_form="tiles"):
+                            core_form="tiles", pis_shell="torch"):
     """build_objective under TRAIN.BACKEND: hip.  The options the fit kernels do not cover raise
     NotImplementedError naming the option; the network itself is checked at the first batch.
     make: `device_objective`, or `device_step` under TRAIN.FUSED_STEP."""
-    form = {} if core_form == "tiles" else {"core_form": core_form}  # the default reproduces the calls as they were
+    form = {} if core_form == "tiles" else {"core_form": core_form}  # the defaults reproduce the calls as they were
+    if pis_shell != "torch":
+        form["pis_shell"] = pis_shell
     loss_cfg = train_cfg["LOSS"]
     beta = float(loss_cfg["beta"])
     loss_fn = make_loss_fn(loss_cfg.get("FN"))

@@ -233,7 +233,8 @@ class PicardRunner:
         objective, self.fit_kind = build_objective(t, self.equation.nx, self.supervise_gradient,
                                                    self.supervise_hessian, self.output_dim,
                                                    backend=str(t.get("BACKEND", "torch")), fused_step=fused,
-                                                   core_form=str(t.get("CORE_FORM", "tiles")))
+                                                   core_form=str(t.get("CORE_FORM", "tiles")),
+                                                   pis_shell=str(t.get("PIS_SHELL", "torch")))
         steps = fused_train_steps if fused else train_steps
         self.fit_step = "fused" if fused else "torch"
         opt, sched = make_optimizer(net.parameters(), t.OPTIMIZER)

@@ -38,6 +38,9 @@
  *   dpi_fit_core_layers_forward / dpi_fit_core_layers_backward  picard/solution.py:138-289  PISGradNet's nn_module
  *                            and its double backward as dpi_fit_core_forward / _backward compute them, one launch
  *                            per layer and pass (dpi_fit_core_layers_workspace_bytes: their workspace)
+ *   dpi_fit_shell_forward / dpi_fit_shell_loss / dpi_fit_shell_backward  picard/solution.py:138-289 +
+ *                            picard/solution_jac.py:167-213  what PISGradNet.forward and training_step compute
+ *                            around nn_module, and its backward (dpi_fit_shell_workspace_bytes: their workspace)
  */
 #ifndef DPI_H_
 #define DPI_H_
@@ -512,6 +515,42 @@ int dpi_fit_core_layers_forward(int nx, int n_hidden, const int* widths, const f
 int dpi_fit_core_layers_backward(int nx, int n_hidden, const int* widths, const float* const* W,
                                  const float* const* b, float* const* dW, float* const* db, const float* e,
                                  const float* r, int B, float* dtau, void* ws, size_t ws_bytes, void* stream);
+
+/* --- the shell of a PISGradNet fit (additions within ABI 8; TRAIN.PIS_SHELL: hip): what surrounds the core
+ * primitive above, in three stages that compose with either form of the core.  Per batch row (t, x):
+ *   lambda = T - t, emb = (sin, cos)(coeff lambda + phase), tau = t_encoder(emb),
+ *   s = smooth_net(emb)[0] - smooth_net(emb at lambda = 0)[0], c = exp(-lambda / 2),
+ *   res = g(c x), res_x = c g_x(c x)                                             (dpi_fit_shell_forward)
+ *   u = s sp + (1 - s) res, u_x = s q + (1 - s) res_x, w = exp(beta t),
+ *   v_loss = mean w rho(u - y_0), g_loss_d = mean w rho(u_x,d - y_d), total = v_loss + kappa sum_d g_loss_d,
+ *   e = d total / d sp, r = d total / d q, sbar = d total / d s                   (dpi_fit_shell_loss)
+ *   the gradients of t_encoder, smooth_net and timestep_phase from taubar (the core's backward) and sbar; the
+ *   zero point of s is one evaluation, whose cotangent is -sum_rows sbar           (dpi_fit_shell_backward)
+ * params / grads: the time networks' tensors in state-dict order, 5 + 2 (n_smooth_hidden + 2) device pointers:
+ * timestep_phase (1, 64); t_encoder.0 weight (64, 128), bias; t_encoder.2 weight (64, 64), bias; smooth_net's
+ * Linear layers: (64, 128), n_smooth_hidden x (64, 64), (nx, 64), each weight then bias.  coeff: the
+ * timestep_coeff buffer (64).  n_smooth_hidden = len(NETWORK.NEURONS), 1 - 4; nx <= 128; 64 channels; p an OU
+ * problem (dpi_problem_create_ou, at most 8 mixture components) of the same nx: DPI_ERR_UNSUPPORTED / DPI_ERR_ARG
+ * name the cap.  B >= 1 (the loss is a mean over the batch).  tx (B, tx_stride >= 1 + nx), y (B, y_stride >=
+ * 1 + nx); tau (B, 64), s, res, e, sbar (B), res_x, q, r (B, nx), sp (B), dtau (B, 64), losses (2 + nx:
+ * total, v_loss, g_loss[nx], the layout of dpi_fit_gradients).  grad = 0: res_x is not written (may be NULL).
+ * kappa <= 1e-9 or q NULL is the value kind: res_x and r are not read or written, only the value column of
+ * losses and the value part of sbar are formed.  Of smooth_net's last layer only row 0 of the weight has a
+ * gradient: its other rows and its whole bias are written as exact zeros.  Conventions of dpi_fit_core_*: on
+ * `stream`, no host synchronisation, no atomics, every output overwritten, all sums over rows in fp64 in fixed
+ * row order (bitwise reproducible), arguments checked before any device work.  ws: 8-byte aligned, >=
+ * dpi_fit_shell_workspace_bytes(nx, n_smooth_hidden, B) bytes (0 for a refused shape), the same one for the
+ * three calls of a batch: the forward parks what the backward reads. */
+size_t dpi_fit_shell_workspace_bytes(int nx, int n_smooth_hidden, int B);
+int dpi_fit_shell_forward(dpi_problem p, double T, int nx, int n_smooth_hidden, const float* coeff,
+                          const float* const* params, const float* tx, int tx_stride, int B, int grad, float* tau,
+                          float* s, float* res, float* res_x, void* ws, size_t ws_bytes, void* stream);
+int dpi_fit_shell_loss(int nx, const float* sp, const float* q, const float* s, const float* res,
+                       const float* res_x, const float* tx, int tx_stride, const float* y, int y_stride, int B,
+                       float beta, int loss_kind, float clip, float kappa, float* losses, float* e, float* r,
+                       float* sbar, void* ws, size_t ws_bytes, void* stream);
+int dpi_fit_shell_backward(int nx, int n_smooth_hidden, const float* const* params, float* const* grads,
+                           const float* dtau, const float* sbar, int B, void* ws, size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

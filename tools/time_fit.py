@@ -20,6 +20,10 @@ baseline; --form fused|unfused runs that one form alone once per shape (for a ke
 --core-form tiles|layers (TRAIN.CORE_FORM) times, for the two PISGradNet shapes, the device objective with that
 form of the core against torch; with --against-tiles, "layers" against "tiles" instead, alternating in the
 same way; with --form-alone, that form alone once per shape (for a kernel trace).
+
+--pis-shell hip (TRAIN.PIS_SHELL), with --core-form: the device objective with the shell in HIP ("shell-hip": the
+time networks, the g0 part and the loss from dpi_fit_shell_*) against the same core form with the shell in torch
+("shell-torch", the baseline); with --form-alone, "shell-hip" alone once per shape.
 """
 import argparse
 import json
@@ -47,13 +51,16 @@ def make_net(name, nx, widths):
     return dpi.PISGradNet(hidden_shapes=list(widths), dim=nx, g0=eq.g, T=1.0)
 
 
-def time_steps(name, backend, B, nx, widths, c, reps, warmup):
+def time_steps(name, backend, B, nx, widths, c, reps, warmup, core_form=None):
     torch.manual_seed(0)
     net = make_net(name, nx, widths).to("cuda")
     scaler = fit.FixedLossScaler(c)
     make = {"hip": fit.device_objective, "unfused": fit.device_objective, "fused": fit.device_step,
-            "torch": fit.gradient_objective, "tiles": fit.device_objective, "layers": fit.device_objective}[backend]
+            "torch": fit.gradient_objective, "tiles": fit.device_objective, "layers": fit.device_objective,
+            "shell-hip": fit.device_objective, "shell-torch": fit.device_objective}[backend]
     form = {"core_form": backend} if backend in ("tiles", "layers") else {}
+    if backend.startswith("shell-"):
+        form = {"core_form": core_form, "pis_shell": backend[len("shell-"):]}
     objective = make(0.0, torch.square, scaler, nx, **form)
     steps = fit.fused_train_steps if backend == "fused" else fit.train_steps
     opt = torch.optim.Adam(net.parameters(), lr=1e-3)
@@ -88,6 +95,8 @@ def main():
                     help="the PISGradNet shapes with this form of the core (TRAIN.CORE_FORM) against torch")
     ap.add_argument("--against-tiles", action="store_true", help="with --core-form layers: against tiles, not torch")
     ap.add_argument("--form-alone", action="store_true", help="with --core-form: run that form alone, once")
+    ap.add_argument("--pis-shell", choices=("hip",), default=None,
+                    help="with --core-form: the shell in HIP (TRAIN.PIS_SHELL) against the shell in torch, same core form")
     a = ap.parse_args()
     assert a.reps >= 20, "the median of at least 20 steps"
     forms = a.step_forms or a.form is not None
@@ -99,16 +108,21 @@ def main():
     if core:
         new, old = a.core_form, "tiles" if a.against_tiles else "torch"
     alone = a.form if a.form is not None else (a.core_form if a.form_alone else None)
+    assert core or a.pis_shell is None, "--pis-shell goes with --core-form"
+    assert not (a.pis_shell and a.against_tiles), "--pis-shell compares the shells, --against-tiles the core forms"
+    if a.pis_shell:
+        new, old = "shell-hip", "shell-torch"
+        alone = new if a.form_alone else None
     for name, B, nx, widths, c in [s for s in SHAPES if a.only in s[0] and not (forms and "pisgradnet" in s[0])
                                    and not (core and "pisgradnet" not in s[0])]:
         if alone is not None:
-            r = time_steps(name, alone, B, nx, widths, c, a.reps, a.warmup)
+            r = time_steps(name, alone, B, nx, widths, c, a.reps, a.warmup, a.core_form)
             print(json.dumps({"shape": name, "backend": alone, **r}), flush=True)
             continue
         runs = {new: [], old: []}
         for _ in range(a.pairs):
             for backend in (new, old):
-                r = time_steps(name, backend, B, nx, widths, c, a.reps, a.warmup)
+                r = time_steps(name, backend, B, nx, widths, c, a.reps, a.warmup, a.core_form)
                 runs[backend].append(r["ms_median"])
                 print(json.dumps({"shape": name, "backend": backend, **r}), flush=True)
         spread = max(runs[old]) - min(runs[old])
